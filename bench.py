@@ -15,6 +15,14 @@ secrets per GPU.  Inputs are generated on the device before the timed region, in
                                              (all-gather of the party slabs + reconstruct on every rank) is the timed step
     python bench.py --gpus 8 --config c5     BASELINE configs[4]: 10^9 Mersenne61 secrets (128,42) in all, split over the
                                              ranks; share (matrix cores) + reconstruct of the rank's shard per step
+    python bench.py --full                   the headline and, after it, everything else this file measures (below)
+    python bench.py --dump-outputs DIR       after the timed steps, what the last step computed as DIR/<name>.npy
+
+A plain run is the headline alone: set-up, warm-up, the timed steps, the outputs if --dump-outputs names a directory, the
+line.  The legs after the headline (the open step, the other configurations, the PRG mode, additive sharing, the
+element-wise path, the layout bridge, Matrix::multiply, the CPU baseline, the measured copy rate, the opt-in live PMC
+passes) and the detail file by default run only under --full; their own switches (--open, --configs, --ew, --cpu-sample,
+--pmc-live ..) choose among them there.
 
 Multi-GPU: the batch of independent secrets shards across ranks (rank r owns its own N secrets,
 weak scaling, no data-path collective); time = max over ranks.  The one exchange step of the path, the MPC
@@ -48,13 +56,24 @@ from bench_legs.pmc import (KERNEL_SOURCES, PMC_CONFIGS, PMC_NEEDLES, kernel_sou
 
 LINE_LIMIT = 8000        # bytes of the result line; the driver's record of round 5 lost a 20 KB line
 DEFAULT_DETAIL = os.path.join(ROOT, "bench_detail.json")
+DUMP_BUDGET = 60 << 20   # bytes of arrays --dump-outputs writes in all (a fixed, seeded sample of the secrets past it)
+DUMP_MAX_SECRETS = 1 << 18
+DUMP_SEED = 20241016
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; --config c5: 5)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; --config c5: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg (open step, configurations, element-wise path, CPU baseline, "
+                         "measured copy rate, live PMC passes when asked) and the detail file by default; a plain run times "
+                         "the headline alone")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (the share matrix and the reconstructed "
+                         "secrets of rank 0's shard; a fixed, seeded sample of the secrets past %d MB) as DIR/<name>.npy, "
+                         "float64, every 64-bit limb as its low and high 32-bit halves" % (DUMP_BUDGET >> 20))
     ap.add_argument("--mode", default="path", choices=["path", "open"],
                     help="path: share + reconstruct per step (the headline); open: only the cross-party open step")
     ap.add_argument("--config", default="c2", choices=["c2", "c4", "c5"],
@@ -98,11 +117,59 @@ def parse_args(argv=None):
     ap.add_argument("--side-timeout", type=float, default=300.0,
                     help="multi-rank runs: seconds the legs after the headline (RCCL through torch and through the C ABI) may take "
                          "before rank 0 writes the line with what it has and every rank exits (0 = no limit)")
-    ap.add_argument("--detail", default=DEFAULT_DETAIL,
-                    help="where rank 0 writes the detail file (everything the legs measured); '' = nowhere")
+    ap.add_argument("--detail", default=None,
+                    help="where rank 0 writes the detail file (everything the legs measured); '' = nowhere (default: "
+                         "bench_detail.json next to this script under --full, nowhere otherwise)")
     ap.add_argument("--inject-error", default="", choices=["", "c_abi", "hang"],
                     help="tests only: make the named side leg fail, to see the line report it and the exit code follow")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    c5 = args.config == "c5"          # a (128,42) step is ~80 ms per 1.25e8 secrets
+    if args.steps is None:
+        args.steps = 5 if c5 else 20
+    if args.warmup is None:
+        args.warmup = 1 if c5 else 3
+    if args.detail is None:
+        args.detail = DEFAULT_DETAIL if args.full else ""
+    if args.dump_outputs and (args.dry_run or args.config == "c4" or args.mode == "open"):
+        ap.error("--dump-outputs: only the share + reconstruct path computes outputs (not --dry-run, --config c4 or --mode open)")
+    return args
+
+
+def dump_sample(N, bytes_per_secret, budget=DUMP_BUDGET):
+    """the secrets --dump-outputs writes: all N when they fit in the budget, else a sorted sample of them drawn with a fixed
+    seed (the same indices in every run of the same arguments)"""
+    import numpy as np
+    S = min(N, DUMP_MAX_SECRETS, max(1, budget // bytes_per_secret))
+    if S == N:
+        return np.arange(N, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=S, replace=False)).astype(np.int64)
+
+
+def exact_f64(limbs):
+    """element tensors' bits (int64 holding uint64 limbs, [..., L]) as float64 without rounding: [..., L, 2], each limb's low
+    and high 32-bit halves"""
+    import numpy as np
+    u = np.ascontiguousarray(limbs).view(np.uint64)
+    return np.stack([(u & np.uint64(0xFFFFFFFF)).astype(np.float64), (u >> np.uint64(32)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(path, shares, out):
+    """DIR/shares.npy [n][S][L][2], DIR/secrets.npy [S][L][2] (the reconstructed secrets) and DIR/sample_index.npy [S]: the
+    columns of the sample of dump_sample, gathered on the device.  Returns the number of bytes written."""
+    import numpy as np
+    import torch
+    n, N, L = shares.shape
+    idx = dump_sample(N, (n + 1) * L * 16 + 8)
+    di = torch.from_numpy(idx).to(shares.device)
+    arrays = {"shares": exact_f64(shares.index_select(1, di).cpu().numpy()),
+              "secrets": exact_f64(out.index_select(0, di).cpu().numpy()),
+              "sample_index": idx.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    return total
 
 
 def self_launch(args):
@@ -242,6 +309,8 @@ def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)          # never returns
+    if not args.full:              # a plain run: the headline alone, no leg after it
+        args.open = args.configs = args.ew = args.cpu_sample = args.cpu_all_cores = args.pmc_live = 0
 
     # The contract is ONE line on stdout.  Libraries write there too (RCCL prints a version banner from ncclCommInitRank
     # when NCCL_DEBUG asks for it): from here on file descriptor 1 goes to stderr, and the result line alone is written to
@@ -354,8 +423,6 @@ def main():
     if pl["key"] == "c5":
         args.field, args.n, args.t, args.secrets = pl["field"], pl["n"], pl["t"], pl["mine"]
         args.configs = args.open = 0
-        if args.steps == 20 and args.warmup == 3:   # the defaults are the headline's: a (128,42) step is ~80 ms per 1.25e8
-            args.steps, args.warmup = 5, 1
         args.cpu_sample = min(args.cpu_sample, 20_000)
     f, L = ctx.tag_limbs(args.field)
     E = 8 * L
@@ -412,22 +479,30 @@ def main():
         flag = torch.tensor([1 if verified else 0], dtype=torch.int64, device="cpu" if args.backend == "gloo" else "cuda")
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         verified = bool(flag.item())
+    if args.dump_outputs and rank == 0:
+        _, _, last_shares, last_out = sets[(args.steps - 1) % nsets]      # the set the last timed step ran on
+        nbytes = dump_outputs(args.dump_outputs, last_shares, last_out)
+        print(f"bench.py: outputs of the last step in {args.dump_outputs} ({nbytes / 2**20:.1f} MiB)", file=sys.stderr)
+        del last_shares, last_out
     secrets, coeffs, shares, out = sets[0]
     del sets[1:]
     ctx.free()
 
-    # measured copy bandwidth of the same device (read+write bytes / time), for context
-    probe_bytes = min(4 << 30, shares.numel() * 8 // 2) & ~15
-    src = shares.view(-1)[: probe_bytes // 8]
-    dst = shares.view(-1)[probe_bytes // 8: 2 * (probe_bytes // 8)]
-    scl.stream_copy(dst, src)
-    tm = scl.Timer()
-    tm.start()
-    for _ in range(5):
+    copy_gbps = None
+    if args.full:
+        # measured copy bandwidth of the same device (read+write bytes / time), for context
+        probe_bytes = min(4 << 30, shares.numel() * 8 // 2) & ~15
+        src = shares.view(-1)[: probe_bytes // 8]
+        dst = shares.view(-1)[probe_bytes // 8: 2 * (probe_bytes // 8)]
         scl.stream_copy(dst, src)
-    tm.stop()
-    copy_gbps = 2 * probe_bytes * 5 / (tm.elapsed_ms() * 1e-3) / 1e9
-    del secrets, coeffs, shares, out, src, dst, sets
+        tm = scl.Timer()
+        tm.start()
+        for _ in range(5):
+            scl.stream_copy(dst, src)
+        tm.stop()
+        copy_gbps = 2 * probe_bytes * 5 / (tm.elapsed_ms() * 1e-3) / 1e9
+        del src, dst
+    del secrets, coeffs, shares, out, sets
     ctx.free()
 
     def headline_line(rccl):
@@ -445,7 +520,7 @@ def main():
                     "frac": ach / HBM_PEAK_GBPS, "traffic": traffic, "algorithmic_bytes": algo,
                     "traffic_over_algorithmic": (traffic / algo) if traffic else None,
                     "traffic_source": "stamped: profiles/pmc_traffic.json" if traffic else None,
-                    "measured_copy_GBps": copy_gbps, "frac_of_measured_copy": ach / copy_gbps}
+                    "measured_copy_GBps": copy_gbps, "frac_of_measured_copy": ach / copy_gbps if copy_gbps else None}
         if dom == "shamir_share" and args.share_mode == "coeffs" and on_matrix_cores(args.field, n, t):
             # --config c5: the dominant kernel runs on the matrix cores; its HBM-equivalent figures stay beside the matrix roofline
             hbm = roofline

@@ -122,8 +122,8 @@ def pmc_report(fetch, write, copy_bytes):
 
 
 def live_pmc_traffic(args, bench_py, timeout_s=240):
-    """HBM bytes per launch OBSERVED in this run: two child processes run this command's GPU legs once more (headline 3 steps,
-    the side configurations when --configs is on; no open step, no CPU baseline) under `rocprofv3 --pmc FETCH_SIZE` and
+    """HBM bytes per launch OBSERVED in this run: two child processes run this command's GPU legs once more (bench.py --full:
+    headline 3 steps, the copy probe k_copy16, the side configurations when --configs is on; no open step, no CPU baseline) under `rocprofv3 --pmc FETCH_SIZE` and
     `--pmc WRITE_SIZE` (the two cannot share a pass on gfx950; no trace domain is combined with --pmc), and pmc_report reads the
     kernels' counter means from their CSVs.  The program itself follows `--`.  Children of this process, started after every
     timed region.  Returns (report or None, info): info = {"ran", "seconds", "fallback_reason"} goes into the detail file as
@@ -140,7 +140,7 @@ def live_pmc_traffic(args, bench_py, timeout_s=240):
     if any(k.startswith(("ROCP_", "ROCPROF")) for k in os.environ):   # this process is itself being profiled: no nesting
         return done(None, "this process is itself running under a profiler")
     work = tempfile.mkdtemp(prefix="scl_pmc_", dir="/tmp")
-    child = [sys.executable, bench_py, "--configs", str(args.configs), "--open", "0", "--cpu-sample", "0",
+    child = [sys.executable, bench_py, "--full", "--configs", str(args.configs), "--open", "0", "--cpu-sample", "0",
              "--pmc-live", "0", "--ew", "0", "--allocations", "1", "--steps", "3", "--warmup", "1", "--field", args.field,
              "--n", str(args.n), "--t", str(args.t), "--secrets", str(args.secrets), "--share-mode", args.share_mode,
              "--detail", os.path.join(work, "detail.json")]

@@ -1,15 +1,15 @@
 // tests/cxx/ref_gf7_inplace.cc -- the reference's OWN worked example of its field plug-in boundary,
-// /root/reference/test/scl/gf7.h + gf7.cc (a traits struct and the ff:: specialisations for the integers modulo 7), compiled
+// test/scl/gf7.h + gf7.cc of the reference (a traits struct and the ff:: specialisations for the integers modulo 7), compiled
 // IN PLACE -- the two files are handed to the compiler where they lie, nothing of them is copied -- against this repo's
 // mirror headers: an include directory in which `scl` is a link to include/scl_hip makes the reference's
-// `#include "scl/math/fields/ff_ops.h"` resolve to include/scl_hip/math/fields/ff_ops.h (tests/test_cxx_api.py builds
+// `#include "scl/math/fields/ff_ops.h"` resolve to include/scl_hip/math/fields/ff_ops.h (make -C oracle gf7 builds
 // it; CPU only, skipped where the reference is absent).  What it shows: a field defined the reference's way compiles
 // unchanged and runs through FF / Vector / Polynomial / computeLagrangeBasis / scl::ss of the mirror.
 // Cases: test/scl/ss/test_shamir.cc:144-160 (Berlekamp-Welch, the Wikipedia example) and the identities of
 // test/scl/math/test_ff.cc:64-227 that need no hex parsing (gf7.cc has no convertTo(string)).
 #include <cstdio>
 
-#include "gf7.h"      // -I /root/reference/test/scl
+#include "gf7.h"      // -I <reference>/test/scl
 #include "scl/scl.h"  // -I <alias directory>: include/scl_hip/scl.h
 
 using namespace scl;

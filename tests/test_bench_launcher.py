@@ -132,6 +132,36 @@ def test_c5_on_fewer_gpus_is_capacity_bound_and_says_so():
     assert bench.plan(bench.parse_args([]), 4, 0)["total"] == 400_000_000
 
 
+def test_plain_run_options_and_output_dump_helpers():
+    """A plain run is the headline alone (--full off, no detail file by default); --steps / --warmup are what the run times
+    whatever the configuration (c5 only has its own defaults); --dump-outputs refuses the modes that compute no outputs; the
+    dumped arrays hold every bit of the field elements in float64 and sample the same secrets in every run."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    a = bench.parse_args([])
+    assert a.full is False and a.detail == "" and a.dump_outputs == "" and (a.steps, a.warmup) == (20, 3)
+    a = bench.parse_args(["--full"])
+    assert a.full is True and a.detail == bench.DEFAULT_DETAIL
+    assert (lambda x: (x.steps, x.warmup))(bench.parse_args(["--config", "c5"])) == (5, 1)
+    assert (lambda x: (x.steps, x.warmup))(bench.parse_args(["--config", "c5", "--steps", "20", "--warmup", "3"])) == (20, 3)
+    for extra in (["--dry-run"], ["--config", "c4"], ["--mode", "open"]):
+        r = _run(["--dump-outputs", "unused"] + extra)
+        assert r.returncode != 0 and "--dump-outputs" in r.stderr, extra
+    u = np.array([[0, 1], [2**64 - 1, 2**61 - 2], [2**32, 2**32 - 1]], dtype=np.uint64)
+    f = bench.exact_f64(u.view(np.int64))
+    assert f.dtype == np.float64 and f.shape == (3, 2, 2)
+    assert np.array_equal(f[..., 0].astype(np.uint64) | (f[..., 1].astype(np.uint64) << np.uint64(32)), u)
+    assert np.array_equal(bench.dump_sample(1000, 176), np.arange(1000))
+    s = bench.dump_sample(100_000_000, 176)
+    assert len(s) == bench.DUMP_MAX_SECRETS and np.array_equal(s, bench.dump_sample(100_000_000, 176))
+    assert np.all(np.diff(s) > 0) and s[-1] < 100_000_000
+    for n, L in ((10, 1), (128, 1), (10, 4)):
+        per = (n + 1) * L * 16 + 8
+        assert len(bench.dump_sample(10**9, per)) * per <= bench.DUMP_BUDGET <= 64 << 20
+
+
 def test_matrix_core_share_is_priced_against_the_matrix_pipe():
     """C5's share kernel runs on the matrix cores: bench.py quotes it against the int8 matrix peak (its HBM-equivalent rate
     stays beside it), only for the shapes capi.hip sends there, with the formulation's own operation count."""

@@ -2280,12 +2280,12 @@ def test_c5_shard_size(scl, port):
 
 
 def test_bench_contract_small(scl):
-    """bench.py end to end on a small batch: ONE compact JSON line on stdout with the contract's keys, the roofline, kernels and
+    """bench.py --full end to end on a small batch: ONE compact JSON line on stdout with the contract's keys, the roofline, kernels and
     cpu_baseline objects and the verdict over every leg -- short enough for the driver's record -- and, in the detail file it
     names, everything the legs measured: the open-step report, the element-wise path with its compute rooflines and the
     asynchronous inverse, the layout bridge, Matrix::multiply, the full CPU baseline."""
     from bench_util import assert_compact, run_bench
-    r = run_bench(["--secrets", "300000", "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--cpu-all-cores", "1",
+    r = run_bench(["--full", "--secrets", "300000", "--steps", "2", "--warmup", "1", "--cpu-sample", "2000", "--cpu-all-cores", "1",
                    "--configs", "0", "--open-secrets", "50000", "--open-chunk", "20000", "--c4-rank-secrets", "60001",
                    "--ew-elements", "300001"], timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -2336,7 +2336,7 @@ def test_bench_contract_small(scl):
     c4 = detail["open"]["c4_all_gather"]
     assert c4["verified"] is True and c4["secrets"] == 50000 and c4["chunk"] == 20000 and c4["parties_per_rank"] == 40
     assert detail["open"]["m61_partial_sums"]["verified"] is True
-    bad = run_bench(["--secrets", "300000", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--configs", "0",
+    bad = run_bench(["--full", "--secrets", "300000", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--configs", "0",
                      "--open-secrets", "50000", "--open-chunk", "20000", "--c4-rank-secrets", "0", "--ew", "0", "--inject-error", "c_abi"],
                     timeout=600)
     bl = assert_compact(bad)
@@ -2346,8 +2346,8 @@ def test_bench_contract_small(scl):
 
 
 def test_bench_default_command_prints_one_short_line(scl):
-    """The driver's own command at full size -- `python3 bench.py --gpus 1 --steps 20 --warmup 5`: BASELINE configs[1], 10^8
-    secrets, every leg on -- prints ONE line of less than 8 KB that parses and carries `roofline` and `cpu_baseline`
+    """The driver's own command at full size with every leg on -- `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`:
+    BASELINE configs[1], 10^8 secrets -- prints ONE line of less than 8 KB that parses and carries `roofline` and `cpu_baseline`
     (BENCH_r05.json: a 20 KB line, "parsed": null), and finishes in about half a minute."""
     import gc
     import time
@@ -2355,7 +2355,7 @@ def test_bench_default_command_prints_one_short_line(scl):
     gc.collect()
     torch.cuda.empty_cache()      # this process's cached blocks go back: the (128,42) shard alone takes 172 of the 288 GB
     t0 = time.time()
-    r = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=900)
+    r = run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], timeout=900)
     wall = time.time() - t0
     assert r.returncode == 0, r.stderr[-3000:]
     line = assert_compact(r)
@@ -2373,14 +2373,82 @@ def test_bench_default_command_prints_one_short_line(scl):
     assert wall < 120, wall
 
 
+def test_bench_plain_command_is_the_headline_alone(scl, tmp_path):
+    """`python3 bench.py --gpus 1 --steps 20 --warmup 5` without --full: set-up, warm-up, the 20 timed steps of BASELINE
+    configs[1] and the line -- no leg after the headline, no detail file unless asked -- in at most 30 s beside its steps."""
+    import gc
+    import subprocess
+    import sys
+    import time
+    gc.collect()
+    torch.cuda.empty_cache()
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    t0 = time.time()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, timeout=600)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["metric"] == "shamir_reconstructions_per_sec" and line["unit"] == "reconstructions/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u64" and line["steps"] == 20 and line["warmup"] == 5
+    assert line["verified"] is True and line["config"]["secrets_per_gpu"] == 100_000_000
+    assert abs(line["value"] - 1e8 / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+    assert "cpu_baseline" not in line and not line["legs"] and not line["verified_legs"] and line.get("detail") is None
+    assert line["roofline"]["measured_copy_GBps"] is None and 0.5 < line["roofline"]["frac"] < 1
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")) <= 64 << 20
+    assert wall - 25 * line["ms_per_step"] * 1e-3 < 30, (wall, line["ms_per_step"])
+
+
+def test_bench_dumps_what_its_last_step_computed(scl, port, tmp_path):
+    """--dump-outputs DIR: the share matrix and the reconstructed secrets of the last timed step, on a fixed, seeded sample of
+    the secrets, in float64 (each 64-bit limb as its two 32-bit halves).  Two runs of the same arguments write the same arrays;
+    the arrays are the oracle's shares of the seeded inputs of the operand set that step ran on, and those secrets."""
+    import bench
+    from bench_util import assert_compact, run_bench
+    N, n, t, steps = 300000, 10, 3, 3
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = run_bench(["--secrets", str(N), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d)], timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = assert_compact(r)
+        assert line["steps"] == steps and line["verified"] is True and "cpu_baseline" not in line
+        assert set(r.detail) == {"by_allocation", "line"}          # no leg ran after the headline
+        runs.append({name: np.load(d / f"{name}.npy") for name in ("shares", "secrets", "sample_index")})
+    a, b = runs
+    for name in a:
+        assert a[name].dtype == np.float64 and np.array_equal(a[name], b[name]), name
+    idx = a["sample_index"].astype(np.int64)
+    S = len(idx)
+    assert S == bench.DUMP_MAX_SECRETS < N and np.all(np.diff(idx) > 0) and idx[-1] < N
+    assert a["shares"].shape == (n, S, 1, 2) and a["secrets"].shape == (S, 1, 2)
+
+    def limbs(x):
+        return x[..., 0].astype(np.uint64) | (x[..., 1].astype(np.uint64) << np.uint64(32))
+    # the inputs of the operand set the last step ran on (bench.py: three sets, rotation from set 0; Ctx.fill_random)
+    f, last = O.M61, (steps - 1) % 3
+    seed = b"scl-bench-m61-0"
+    secrets = host(scl, scl.vector_random(f, N, seed + b"-secrets%d" % last))
+    per_row = (N * 8 + 15) // 16
+    coeffs = np.stack([host(scl, scl.vector_random(f, N, seed + b"-coeffs%d" % last, counter0=k * per_row)) for k in range(t)])
+    assert np.array_equal(limbs(a["secrets"]), secrets[idx])
+    cols = idx[np.linspace(0, S - 1, 64).astype(np.int64)]
+    want = soa(port.shamir_share_coeffs(f, secrets[cols], np.ascontiguousarray(np.transpose(coeffs[:, cols], (1, 0, 2))), n))
+    assert np.array_equal(limbs(a["shares"])[:, np.searchsorted(idx, cols)], want)
+
+
 def test_bench_observes_its_hbm_traffic(scl):
     """--pmc-live 1: roofline.traffic is OBSERVED by the run that prints it: after its timed regions bench.py runs the headline
     alone twice as a child under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (no trace domain beside --pmc; the program
     itself after `--`) and reads the two kernels' counters; the doubling of FETCH_SIZE is checked on k_copy16 in the same
     pass.  At 10^7 secrets here: traffic = the algorithmic bytes within 1 %."""
     from bench_util import assert_compact, run_bench
-    r = run_bench(["--secrets", "10000000", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--configs", "0", "--open", "0",
-                   "--ew", "0", "--pmc-live", "1"], timeout=900)
+    r = run_bench(["--full", "--secrets", "10000000", "--steps", "2", "--warmup", "1", "--cpu-sample", "0", "--configs", "0",
+                   "--open", "0", "--ew", "0", "--pmc-live", "1"], timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = assert_compact(r)
     rf = line["roofline"]
@@ -2441,8 +2509,8 @@ def test_bench_two_ranks_rehearsal_on_one_device(scl):
     Started plainly with --gpus 2, so the self-launcher runs too.  Covers the sharded headline, the all-gather open
     (20 parties per rank) and the reduce-scatter partial-sum open; every round trip must verify."""
     from bench_util import assert_compact, run_bench
-    r = run_bench(["--gpus", "2", "--backend", "gloo", "--secrets", "1000000", "--open-secrets", "100000", "--open-chunk", "32768",
-                   "--configs", "0", "--cpu-sample", "0", "--steps", "2", "--warmup", "1"], {"SCL_BENCH_ONE_DEVICE": "1"}, timeout=900)
+    r = run_bench(["--full", "--gpus", "2", "--backend", "gloo", "--secrets", "1000000", "--open-secrets", "100000", "--open-chunk",
+                   "32768", "--configs", "0", "--cpu-sample", "0", "--steps", "2", "--warmup", "1"], {"SCL_BENCH_ONE_DEVICE": "1"}, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = assert_compact(r)
     assert line["n_gpus"] == 2 and line["verified"] is True and line["config"]["parallelism"] == "shard2"
@@ -2491,8 +2559,8 @@ def test_bench_line_survives_a_rank_that_never_reaches_the_open_step(scl):
     exit code 0 on a multi-rank run whose headline verified (the line says what failed; a scaling record must not be lost to a
     side leg), so the launcher reports a finished job."""
     from bench_util import assert_compact, run_bench
-    r = run_bench(["--gpus", "2", "--backend", "gloo", "--secrets", "1000000", "--open-secrets", "100000", "--open-chunk", "32768",
-                   "--configs", "0", "--cpu-sample", "0", "--steps", "2", "--warmup", "1", "--inject-error", "hang",
+    r = run_bench(["--full", "--gpus", "2", "--backend", "gloo", "--secrets", "1000000", "--open-secrets", "100000", "--open-chunk",
+                   "32768", "--configs", "0", "--cpu-sample", "0", "--steps", "2", "--warmup", "1", "--inject-error", "hang",
                    "--side-timeout", "20"], {"SCL_BENCH_ONE_DEVICE": "1"}, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "watchdog" in r.stderr

@@ -11,7 +11,7 @@
 # stops the script: read its log before running anything again.
 #   (a) tools/open_rccl_check.py on 2, 4, 8 ranks: scl_hip_open_all_gather / _partial_gather / _reduce_scatter and their
 #       torch.distributed twins against the CPU oracle, 10^5 secrets, three fields
-#   (b) bench.py --gpus 1, 2, 4, 8: the headline (BASELINE configs[1], weak scaling) -- the compact line of each into
+#   (b) bench.py --gpus 1, 2, 4, 8 --full: the headline (BASELINE configs[1], weak scaling) and the legs after it -- the compact line of each into
 #       scale_N.json, checked: rccl.ranks == N, N entries in ms_per_step_by_rank, verified
 #   (c) bench.py --gpus 8 --config c4 and --config c5: the configurations BASELINE quotes on 8 GPUs, with rccl_busbw_GBps
 # The N = 1 line of (b) is the driver's BENCH command's workload (tests/test_bench_launcher.py checks that on a dry run).
@@ -51,13 +51,13 @@ if [ "$DRY" != 1 ]; then
 fi
 for N in 1 2 4 8; do
   echo "== (b) headline, $N GPU(s)"
-  timeout -k 10 900 python3 bench.py --gpus $N --steps 20 --warmup 5 --detail "$OUT/scale_${N}_detail.json" "${EXTRA[@]}" \
+  timeout -k 10 900 python3 bench.py --gpus $N --steps 20 --warmup 5 --full --detail "$OUT/scale_${N}_detail.json" "${EXTRA[@]}" \
     > "$OUT/scale_$N.json" 2> "$OUT/scale_$N.err" || { echo "FAILED: see $OUT/scale_$N.err"; tail -5 "$OUT/scale_$N.err"; exit 4; }
   check_line "$OUT/scale_$N.json" $N || { echo "FAILED: the line of $N rank(s) does not check"; exit 5; }
 done
 for C in c4 c5; do
   echo "== (c) --config $C on 8 GPUs"
-  timeout -k 10 1500 python3 bench.py --gpus 8 --config $C --detail "$OUT/${C}_8_detail.json" "${EXTRA[@]}" \
+  timeout -k 10 1500 python3 bench.py --gpus 8 --config $C --full --detail "$OUT/${C}_8_detail.json" "${EXTRA[@]}" \
     > "$OUT/${C}_8.json" 2> "$OUT/${C}_8.err" || { echo "FAILED: see $OUT/${C}_8.err"; tail -5 "$OUT/${C}_8.err"; exit 6; }
   check_line "$OUT/${C}_8.json" 8 || { echo "FAILED: the line of --config $C does not check"; exit 7; }
 done
