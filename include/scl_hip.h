@@ -226,7 +226,8 @@ int scl_hip_shamir_share_prg_packed(int field, uint64_t* shares_dev, size_t shar
                                     size_t secret_stride, size_t N, size_t t, size_t n, size_t width,
                                     const unsigned char* seed_host, size_t seed_len, uint64_t counter0, void* stream);
 /* Batched shamirRecoverP (shamir.h:81-104) with the basis hoisted out of the per-secret
- * call: out[s] = sum_{i<m} lambda[i] * shares[i][s]. */
+ * call: out[s] = sum_{i<m} lambda[i] * shares[i][s].  Asynchronous like the other batch calls, the
+ * first call of a process included (GF(2^128) too: no first-use work), so it can be captured into a hipGraph. */
 int scl_hip_shamir_recover(int field, uint64_t* out_dev, const uint64_t* shares_dev,
                            size_t share_stride, const uint64_t* lambda_host, size_t m, size_t N,
                            void* stream);

@@ -1844,15 +1844,6 @@ int scl_hip_shamir_recover(int field, uint64_t* out, const uint64_t* shares, siz
   return SCL_OK;
 }
 
-// k_recover_gf128_pos issues its LDS reads from inline assembly one batch ahead of the `s_waitcnt lgkmcnt` that covers them
-// (kernels.hpp): between the two the compiler believes the destination registers hold data.  The generated code of this
-// toolchain leaves them alone, which is a property of its register allocation, not a guarantee.  So the first GF(2^128)
-// reconstruct of a process runs both launch shapes of that kernel once against k_recover_gf128 (compiler-scheduled reads)
-// on 4096 pseudo-random secrets; if a result differs, the position-table kernel is never used by this process
-// (scl_hip_last_error says so) -- a toolchain change then costs speed, not correctness.  -1 unknown, 1 good, 0 bad.
-static std::atomic<int> g_gfpos_state{-1};
-static std::mutex g_gfpos_mu;
-
 extern "C++" {
 template <class FieldG>
 static int launch_gfpos(bool big_block, u64* out, const u64* shares, size_t stride, const BigTable<Gf128>& big, size_t m, size_t N,
@@ -1870,47 +1861,6 @@ static int launch_gfpos(bool big_block, u64* out, const u64* shares, size_t stri
     hipLaunchKernelGGL(kern, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(1024), lds, st, out, shares, stride, big, (int)m, N);
   }
   LAUNCH_CHECK();
-  return SCL_OK;
-}
-
-template <class FieldG>
-static int gfpos_usable(bool* usable) {
-  int stt = g_gfpos_state.load();
-  if (stt < 0) {
-    std::lock_guard<std::mutex> lk(g_gfpos_mu);
-    stt = g_gfpos_state.load();
-    if (stt < 0) {
-      constexpr size_t N = 4096, M = 7;  // 7 parties: two groups of five, the second one padded
-      u64 *sh = nullptr, *o = nullptr;
-      HIP_TRY(hipMalloc(&sh, M * N * 16));
-      HIP_TRY(hipMalloc(&o, 3 * N * 16));
-      auto body = [&]() -> int {
-        const unsigned char seed[] = "gfpos self-check";
-        SCL_TRY(scl_hip_prg_blocks(reinterpret_cast<unsigned char*>(sh), M * N, seed, sizeof seed - 1, 0, nullptr));
-        BigTable<Gf128> big;
-        for (size_t i = 0; i < M; ++i) big.v[i] = ((u128)(0x9E3779B97F4A7C15ull * (i + 1)) << 64) | (0xD1B54A32D192ED03ull * (i + 7));
-        hipLaunchKernelGGL(k_recover_gf128<FieldG>, dim3(grid_for(N)), dim3(BLOCK), 0, nullptr, o, sh, N, big, (int)M, N, (const u64*)nullptr);
-        LAUNCH_CHECK();
-        SCL_TRY(launch_gfpos<FieldG>(false, o + 2 * N, sh, N, big, M, N, nullptr));
-        SCL_TRY(launch_gfpos<FieldG>(true, o + 4 * N, sh, N, big, M, N, nullptr));
-        std::vector<u64> h(6 * N);
-        HIP_TRY(hipMemcpy(h.data(), o, h.size() * 8, hipMemcpyDeviceToHost));
-        const bool same = std::equal(h.begin(), h.begin() + 2 * N, h.begin() + 2 * N) &&
-                          std::equal(h.begin(), h.begin() + 2 * N, h.begin() + 4 * N);
-        g_gfpos_state.store(same ? 1 : 0);
-        if (!same)
-          std::fprintf(stderr, "libscl_hip: k_recover_gf128_pos failed its self-check against k_recover_gf128 on this toolchain; "
-                               "GF(2^128) reconstruction uses the shared-shift table kernel instead\n");
-        return SCL_OK;
-      };
-      const int rc = body();
-      (void)hipFree(sh);
-      (void)hipFree(o);
-      if (rc != SCL_OK) return rc;
-      stt = g_gfpos_state.load();
-    }
-  }
-  *usable = stt == 1;
   return SCL_OK;
 }
 
@@ -1942,14 +1892,13 @@ static int recover_block(int field, uint64_t* out, const uint64_t* shares, size_
       const long ft = g_force_table.load();
       if (!ft || ft == 3) {  // GF(2^128): nibble-table kernels ("force_table" 3: the shared-shift form at any m)
         const size_t lds = gfpos_lds_bytes(m);
-        bool pos_ok = false;  // the position-table kernel passed its first-use self-check (see gfpos_usable)
-        if (!prev && ft != 3 && lds <= 160 * 1024) SCL_TRY(gfpos_usable<F>(&pos_ok));
+        const bool pos = ft != 3 && lds <= 160 * 1024;  // the position tables of all m parties fit in one CU's LDS
         if (prev) {
           hipLaunchKernelGGL(k_recover_gf128<F>, dim3(grid_for(N)), dim3(BLOCK), 0, S(stream), out, shares, stride, big,
                              (int)m, N, prev);
-        } else if (pos_ok && lds <= 80 * 1024) {  // position tables, two 512-thread workgroups per CU
+        } else if (pos && lds <= 80 * 1024) {  // position tables, two 512-thread workgroups per CU
           SCL_TRY(launch_gfpos<F>(false, out, shares, stride, big, m, N, S(stream)));
-        } else if (pos_ok) {  // one 1024-thread workgroup per CU
+        } else if (pos) {  // one 1024-thread workgroup per CU
           SCL_TRY(launch_gfpos<F>(true, out, shares, stride, big, m, N, S(stream)));
         } else {
           hipLaunchKernelGGL(k_recover_gf128<F>, dim3(grid_for(N)), dim3(BLOCK), 0, S(stream), out, shares, stride, big,

@@ -1727,6 +1727,99 @@ def test_batch_calls_capture_into_a_hip_graph(scl, port):
         assert np.array_equal(host(scl, sh3), soa(port.additive_share(f, b"graph-seed", fresh, 3)))
 
 
+def _gf128_lam_combination(port, sh, lam):
+    """the oracle's sum_i lam[i] * sh[i] over GF(2^128): sh [m][N][2], lam [m][2]"""
+    acc = np.zeros(sh.shape[1:], dtype=np.uint64)
+    for i in range(sh.shape[0]):
+        acc ^= port.ew(O.GF2_128, O.MUL, np.ascontiguousarray(sh[i]), np.ascontiguousarray(np.broadcast_to(lam[i], sh.shape[1:])))
+    return acc
+
+
+# (m, N, row pitch): N = 1 mod 512 leaves one secret in the last 512-secret block; odd pitches put every row at an odd element offset
+GFPOS_CASES = [(7, 4096, 4096)] + [(m, N, pitch) for m in (5, 7, 40, 41, 80)
+                                    for N, pitch in ((4097, 4097), (513, 515), (1025, 1031))]
+
+
+@pytest.mark.parametrize("m,N,pitch", GFPOS_CASES)
+def test_gf128_pos_kernel_matches_the_shared_shift_kernel(scl, port, m, N, pitch):
+    """GF(2^128) reconstruction at m <= 80 on the position-table kernel (k_recover_gf128_pos: two 512-thread workgroups per CU
+    up to m = 40, one of 1024 threads up to 80) against the shared-shift kernel ("force_table" 3: k_recover_gf128) and the
+    oracle, with full-width coefficients.  The first case is the input the library once checked on its first call: 7 x 4096
+    shares from the PRG stream of b"gfpos self-check" and the golden-ratio coefficients."""
+    f = O.GF2_128
+    if (m, N) == (7, 4096):
+        raw = scl.prg_blocks(m * N, b"gfpos self-check")
+        shares = raw.view(torch.int64).reshape(m, N, 2)
+        M64 = (1 << 64) - 1
+        lam = O.from_ints([(((0x9E3779B97F4A7C15 * (i + 1)) & M64) << 64) | ((0xD1B54A32D192ED03 * (i + 7)) & M64)
+                           for i in range(m)], 2)
+    else:
+        base = dev(scl, rand_elems(port, f, m * pitch, b"gfpos-%d-%d-%d" % (m, N, pitch)).reshape(m, pitch, 2))
+        shares = base[:, :N]
+        lam = rand_elems(port, f, m, b"gfpos-lam-%d" % m)
+    want = _gf128_lam_combination(port, host(scl, shares.contiguous()), lam)
+    got = host(scl, scl.shamir_recover(f, shares, lam))
+    scl.set_tuning("force_table", 3)
+    try:
+        shift = host(scl, scl.shamir_recover(f, shares, lam))
+    finally:
+        scl.set_tuning("force_table", 0)
+    assert np.array_equal(shift, want)
+    assert np.array_equal(got, want)
+
+
+_GF128_CAPTURE_CHILD = r"""
+import json, sys
+root = sys.argv[1]
+sys.path[:0] = [root + "/secure-computation-library_amd", root + "/tests"]
+import numpy as np
+import torch
+import oracle_lib as O
+import scl_amd as scl
+
+f, n, t, N = scl.GF2_128, 40, 13, 4097
+torch.cuda.set_device(0)
+port = O.Port()
+nodes = O.from_ints(list(range(1, n + 1)), 2)       # the default nodes: the bit patterns of 1..n
+vdm = port.vandermonde(O.GF2_128, n, t + 1, nodes)
+lam_o = port.lagrange_basis(O.GF2_128, nodes, O.from_ints([0], 2)[0])
+lam = scl.lagrange_basis(f, n)
+assert np.array_equal(lam, lam_o)
+shares, out = scl.empty(f, n, N), scl.empty(f, N)
+g, s = torch.cuda.CUDAGraph(), torch.cuda.Stream()
+with torch.cuda.stream(s):
+    with torch.cuda.graph(g, stream=s):
+        scl.shamir_recover(f, shares, lam, out=out)    # the first GF(2^128) reconstruct of this process
+torch.cuda.synchronize()
+for rep in range(2):
+    sec = port.vector_random(O.GF2_128, b"capture-secrets-%d" % rep, N)
+    rows = np.concatenate([sec[None], port.vector_random(O.GF2_128, b"capture-coeffs-%d" % rep, t * N).reshape(t, N, 2)])
+    sh = port.matmul(O.GF2_128, vdm, rows)                # [n][N]: the oracle's shares at the default nodes
+    shares.copy_(scl.to_device(sh))
+    out.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    got = scl.to_host(out)
+    assert np.array_equal(got, sec), rep
+    want = np.zeros_like(sec)
+    for i in range(n):
+        want ^= port.ew(O.GF2_128, O.MUL, sh[i], np.ascontiguousarray(np.broadcast_to(lam_o[i], sec.shape)))
+    assert np.array_equal(got, want), rep
+print(json.dumps({"ok": True, "replays": 2}))
+"""
+
+
+def test_gf128_first_reconstruct_of_a_process_captures_into_a_hip_graph():
+    """A fresh process whose FIRST GF(2^128) reconstruct is captured into a torch.cuda.CUDAGraph (C4's shape: 40 parties,
+    threshold 13, the position-table kernel): the call neither synchronises nor allocates, the graph replays on new shares and
+    equals the oracle.  In a child process so that no earlier call of this test session has run the path before."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _GF128_CAPTURE_CHILD, ROOT], capture_output=True, text=True, timeout=600)
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert r.returncode == 0 and lines and json.loads(lines[-1])["ok"], r.stdout[-2000:] + r.stderr[-4000:]
+
+
 @pytest.mark.parametrize("f", ALL_FIELDS + [scl_ring for scl_ring in (0x100 + 64, 0x100 + 128)])
 def test_ew_status_leaves_the_zero_flag_on_the_device(scl, port, f):
     """scl_hip_ew_status: FF::inverse / operator/ (ff.h:203-246; the throw of small_ff.h:61-70, ff_ops_gmp.h:250-260,

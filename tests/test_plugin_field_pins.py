@@ -224,6 +224,17 @@ GCM_CASES = [
 ]
 
 
+def spec_mul(X: int, Y: int) -> int:
+    """the multiplication of the GCM specification as it is written there (Algorithm 1: right shifts, R = e1 || 0^120) on
+    blocks as big-endian integers"""
+    Z, V = 0, X
+    for i in range(128):
+        if (Y >> (127 - i)) & 1:
+            Z ^= V
+        V = (V >> 1) ^ (0xe1 << 120) if V & 1 else V >> 1
+    return Z
+
+
 def _gcm_products():
     """(a, b, a * b) as elements of this field, one per GHASH step X_i = (X_{i-1} xor C_i) * H of the published vectors"""
     out = []
@@ -239,15 +250,6 @@ def test_the_gcm_vectors_are_the_published_ones():
     """The constants above, checked two ways that share nothing with the engine: (1) the multiplication of the GCM
     specification as it is written there (Algorithm 1: right shifts, R = e1 || 0^120) reproduces every X_i from H and the
     blocks; (2) where the image has openssl, H is AES_K(0^128) for the keys of the two test cases."""
-    R_ = 0xe1 << 120
-
-    def spec_mul(X, Y):
-        Z, V = 0, X
-        for i in range(128):
-            if (Y >> (127 - i)) & 1:
-                Z ^= V
-            V = (V >> 1) ^ R_ if V & 1 else V >> 1
-        return Z
     for c in GCM_CASES:
         x = 0
         for blk, want in zip(c["blocks"], c["X"]):
