@@ -112,14 +112,13 @@ int scl_hip_timer_start(void* timer, void* stream);
 int scl_hip_timer_stop(void* timer, void* stream);
 int scl_hip_timer_elapsed_ms(void* timer, float* ms); /* synchronises on the stop event */
 /* knobs for tuning and for the tests that pin a kernel path (0 = built-in default unless noted); they belong to the
- * calling host thread:
- *   max_blocks, aes_blocks   grid caps;  nontemporal (default 1);  force_scalar (no 16-byte packs)
+ * calling host thread.  A key not listed here is refused with SCL_ERR_BAD_ARG:
+ *   max_blocks, aes_blocks   grid caps;  force_scalar (no 16-byte packs)
  *   force_table  1: no small-node / blocked / Vandermonde-table share kernels, 2: also no small-node Horner,
  *                3: GF(2^128) reconstruct on the shared-shift nibble tables instead of the position tables
- *   stream_block (default 64) workgroup size of the (m <= 16) reconstruct kernel: 64 or 256
- *   stream_waves (default -1) resident waves per CU that kernel is capped at; 0 = no cap, -1 = 10 for one-word
- *                elements and 12 for wider ones
- *   share_waves  (default 9) the same cap for the Mersenne61 small-node share kernel (threshold compiled in, stream_block
+ *   stream_waves (default -1) resident waves per CU the (m <= 16) reconstruct kernel is capped at; 0 = no cap, -1 = 10
+ *                for one-word elements and 12 for wider ones
+ *   share_waves  (default 9) the same cap for the Mersenne61 small-node share kernel (threshold compiled in, single-wave
  *                workgroups); 0 = the 256-thread kernel with the threshold at run time, no cap
  *   share_waves128 (default 12) the same for the 16-byte fields' small-node share kernel (Mersenne127, Mont128); 0 = the
  *                256-thread kernel
@@ -127,8 +126,6 @@ int scl_hip_timer_elapsed_ms(void* timer, float* ms); /* synchronises on the sto
  *                (row block, k-chunk) form on the sharing kernels instead of the general kernel
  *   open_gather_always (default 0) scl_hip_open_all_gather on a ONE-rank communicator: 1 = through the collective path all the
  *                same (tests); 0 = reconstruct straight from the slab
- *   prg_t3       (default 1) PRG-driven sharing at t = 3 over the Mersenne fields: the fused kernel with the threshold
- *                compiled in; 0 = the fused kernel that takes any t <= 7
  *   gf_tiles     (default 1) GF(2^128) sharing at the default nodes, 5 <= t <= 16: eight nodes per Horner loop; 0 = one node
  *                at a time (the kernel that serves any other small nodes)
  *   prg_two_pass PRG-driven sharing: 1 = always draw the coefficient rows into a temporary and share from there, -1 = always the
@@ -140,10 +137,7 @@ int scl_hip_timer_elapsed_ms(void* timer, float* ms); /* synchronises on the sto
  *                4 | 8 that block length for chains of 32 and more (also Mont128), -1 never; with inv_batch 256 a chain of 256
  *   matmul_lds_min  columns from which the thread-per-column matrix kernels are taken instead of the tiled one (0 = by shape);
  *   transpose_tile  secrets per LDS tile of the 16-byte layout bridge (0 = up to 512);  gemm_slab_mib  digit planes per factor
- *                and launch of the general matrix-core product in MiB (0 = 1024)
- *   mfma_areg    (default 1) matrix-core kernel keeps V's digit fragments in registers for 97..128 parties
- *   mfma_pipe    (default 2) matrix-core kernel for 97..128 parties: 2 = two software-pipelined waves per SIMD on
- *                16x16x64 tiles (thresholds 32..63; smaller ones as 1), 1 = one pipelined wave per SIMD, 0 = word bursts */
+ *                and launch of the general matrix-core product in MiB (0 = 1024) */
 int scl_hip_set_tuning(const char* key, long value);
 /* frees the calling thread's device scratch and temporary arena (for host threads that exit; see Conventions) */
 int scl_hip_thread_cleanup(void);

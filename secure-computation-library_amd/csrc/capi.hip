@@ -70,25 +70,17 @@ SCL_STATE(thread_local std::string g_err);
 // Experiment knobs (scl_hip_set_tuning).  Per host thread, like the Mont128 modulus below: the library keeps no mutable
 // state that two host threads share, so concurrent callers with different settings cannot race (scl_hip.h, Conventions).
 SCL_STATE(thread_local Knob g_max_blocks, {0});
-SCL_STATE(thread_local Knob g_nontemporal, {1});
 SCL_STATE(thread_local Knob g_force_scalar, {0});
 SCL_STATE(thread_local Knob g_force_table, {0});
-SCL_STATE(thread_local Knob g_mfma_tpb, {0});
-// 4-row-tile shapes: 2 = two pipelined waves per SIMD on 16x16x64 tiles (33..64 coefficient rows; else as 1), 1 = one
-// pipelined wave per SIMD, 0 = burst kernel ("mfma_pipe")
-SCL_STATE(thread_local Knob g_mfma_pipe, {2});
-SCL_STATE(thread_local Knob g_mfma_areg, {1});  // register-resident V fragments for the 4-row-tile shapes ("mfma_areg")
 SCL_STATE(thread_local Knob g_mfma, {0});       // 0 auto, 1 always (where applicable), -1 never
 // GF(2^128) sharing at the default nodes: 1 = eight nodes per Horner loop (k_share_gf_tiles), 0 = one node at a time
 // (k_share_gf_nodes) ("gf_tiles")
 SCL_STATE(thread_local Knob g_gf_tiles, {1});
 SCL_STATE(thread_local Knob g_open_gather_always, {0});  // the open step on ONE rank: 1 = still through RCCL's all-gather
-SCL_STATE(thread_local Knob g_prg_t3, {1});  // PRG-driven sharing at t = 3 over the Mersenne fields: 1 = threshold compiled in
 SCL_STATE(thread_local Knob g_prg_two_pass, {0});  // PRG-driven sharing: 0 auto, 1 always two passes, -1 always fused
-// Headline streaming kernels (k_recover_fixed, k_share_small): workgroup size and resident waves per CU
-// (kernels.hpp, "Launch geometry"); "stream_block" 64 | 256, "stream_waves" 0 = no cap
-SCL_STATE(thread_local Knob g_stream_block, {64});
-// -1 = by element size: 10 for one-word elements, 12 for wider ones (profiles/r2_probe_cap_rec.txt, r2_probe_c3_waves.txt)
+// Headline streaming kernels (k_recover_fixed, k_share_small): resident waves per CU (kernels.hpp, "Launch geometry");
+// "stream_waves" 0 = no cap, -1 = by element size: 10 for one-word elements, 12 for wider ones (profiles/r2_probe_cap_rec.txt,
+// r2_probe_c3_waves.txt)
 SCL_STATE(thread_local Knob g_stream_waves, {-1});
 // the same cap for the Mersenne61 small-node share kernel ("share_waves"; 0 = the 256-thread kernel without a cap)
 SCL_STATE(thread_local Knob g_share_waves, {9});
@@ -714,6 +706,8 @@ int mfma_table(const BigTable<M61>& al, size_t n, size_t t, int KS, int MT, DevP
   return SCL_OK;
 }
 
+// The kernel by shape (profiles/r5_probe_auto_choices.txt): four row tiles (65..128 parties) go to the pipelined kernels,
+// k_share_mfma_m61_p16 with two k-steps and k_share_mfma_m61_pipe<1> with one; fewer row tiles to k_share_mfma_m61.
 template <int KS, int MT>
 int launch_share_mfma(u64* shares, size_t stride, const u64* secrets, const u64* coeffs, size_t cstride,
                       const unsigned char* tab, int t, int n, size_t N, hipStream_t st, bool accumulate = false) {
@@ -727,7 +721,7 @@ int launch_share_mfma(u64* shares, size_t stride, const u64* secrets, const u64*
       hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < 256 ? nblocks : 256)), dim3(512), shmem, st, shares, stride, secrets, coeffs,
                          cstride, tab, t, n, N);
     } else {
-      auto kern = &k_share_mfma_m61<KS, MT, false, 512, true>;
+      auto kern = &k_share_mfma_m61<KS, MT, true>;
       const size_t shmem = mf_a_bytes(KS, MT) + mf_b_bytes(KS, MT);
       HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
       const size_t cols = (size_t)2 * (4 / MT) * 32, nblocks = (N + cols - 1) / cols;
@@ -737,66 +731,36 @@ int launch_share_mfma(u64* shares, size_t stride, const u64* secrets, const u64*
     HIP_TRY(hipGetLastError());
     return SCL_OK;
   }
-  const bool areg = g_mfma_areg.load() != 0 && MT == 4;
-  const long tpb_mode = g_mfma_tpb.load();
   if constexpr (MT == 4 && KS == 2) {
-    if (g_mfma_pipe.load() >= 2) {
-      // k_share_mfma_m61_p16: one 8-wave workgroup per CU, 32 secrets per trip, two LDS images of the recoded block
-      const size_t shmem = 2 * mf_b_bytes(KS, MT, 1);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61_p16<>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-      const size_t nblocks = (N + 31) / 32;
-      const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
-      hipLaunchKernelGGL(k_share_mfma_m61_p16<>, dim3(grid), dim3(512), shmem, st, shares, stride, secrets, coeffs, cstride, tab,
-                         t, n, N);
-      HIP_TRY(hipGetLastError());
-      return SCL_OK;
-    }
-  }
-  if constexpr (MT == 4) {
-    if (g_mfma_pipe.load() != 0) {
-      // k_share_mfma_m61_pipe: one 4-wave workgroup per CU, 32 secrets per trip
-      const size_t shmem = mf_b_bytes(KS, MT, 1);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61_pipe<KS>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-      const size_t nblocks = (N + 31) / 32;
-      const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
-      hipLaunchKernelGGL((k_share_mfma_m61_pipe<KS>), dim3(grid), dim3(256), shmem, st, shares, stride, secrets, coeffs,
-                         cstride, tab, t, n, N);
-      HIP_TRY(hipGetLastError());
-      return SCL_OK;
-    }
-  }
-  if (areg && tpb_mode == 256) {
-    constexpr int TPB = 256;
+    // k_share_mfma_m61_p16: one 8-wave workgroup per CU, 32 secrets per trip, two LDS images of the recoded block
+    const size_t shmem = 2 * mf_b_bytes(KS, MT, 1);
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61_p16<>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    const size_t nblocks = (N + 31) / 32;
+    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
+    hipLaunchKernelGGL(k_share_mfma_m61_p16<>, dim3(grid), dim3(512), shmem, st, shares, stride, secrets, coeffs, cstride, tab,
+                       t, n, N);
+  } else if constexpr (MT == 4) {
+    // k_share_mfma_m61_pipe: one 4-wave workgroup per CU, 32 secrets per trip
     const size_t shmem = mf_b_bytes(KS, MT, 1);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61<KS, MT, (MT == 4), TPB>),
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61_pipe<KS>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    const size_t cols = (size_t)(4 / MT) * 32;
-    const size_t nblocks = (N + cols - 1) / cols;
-    const unsigned grid = (unsigned)(nblocks < 512 ? nblocks : 512);  // two 4-wave workgroups per CU
-    hipLaunchKernelGGL((k_share_mfma_m61<KS, MT, (MT == 4), TPB>), dim3(grid), dim3(TPB), shmem, st, shares, stride,
-                       secrets, coeffs, cstride, tab, t, n, N);
-    HIP_TRY(hipGetLastError());
-    return SCL_OK;
-  }
-  const size_t shmem = (areg ? 0 : mf_a_bytes(KS, MT)) + mf_b_bytes(KS, MT);
-  // per device and cheap: set on every call so that multi-device processes are covered
-  if (areg)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61<KS, MT, (MT == 4)>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  else
+    const size_t nblocks = (N + 31) / 32;
+    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
+    hipLaunchKernelGGL((k_share_mfma_m61_pipe<KS>), dim3(grid), dim3(256), shmem, st, shares, stride, secrets, coeffs,
+                       cstride, tab, t, n, N);
+  } else {
+    // k_share_mfma_m61: one 8-wave workgroup per CU, grid-strided; V's digit planes and the recoded block in LDS
+    const size_t shmem = mf_a_bytes(KS, MT) + mf_b_bytes(KS, MT);
+    // per device and cheap: set on every call so that multi-device processes are covered
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61<KS, MT>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-  const size_t cols = (size_t)2 * (4 / MT) * 32;
-  const size_t nblocks = (N + cols - 1) / cols;
-  const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);  // one 8-wave workgroup per CU, grid-strided
-  if (areg)
-    hipLaunchKernelGGL((k_share_mfma_m61<KS, MT, (MT == 4)>), dim3(grid), dim3(512), shmem, st, shares, stride, secrets,
-                       coeffs, cstride, tab, t, n, N);
-  else
+    const size_t cols = (size_t)2 * (4 / MT) * 32;
+    const size_t nblocks = (N + cols - 1) / cols;
+    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
     hipLaunchKernelGGL((k_share_mfma_m61<KS, MT>), dim3(grid), dim3(512), shmem, st, shares, stride, secrets, coeffs,
                        cstride, tab, t, n, N);
+  }
   HIP_TRY(hipGetLastError());
   return SCL_OK;
 }
@@ -1082,7 +1046,7 @@ struct RecoverSmall {
       const long sw = g_stream_waves.load();
       const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 4 ? 10 : 12) : sw, 64, 0);  // (profiles/r5_probe_f3_waves.txt)
       const size_t lanes = F::LIMBS == 4 ? 2 * n : n;  // 32-byte elements: a pair of lanes per secret
-      hipLaunchKernelGGL((k_recover_small<F, M, true, 64>), dim3(grid_for_block(lanes, 64)), dim3(64), pad, st, ctx, out, shares, stride,
+      hipLaunchKernelGGL((k_recover_small<F, M>), dim3(grid_for_block(lanes, 64)), dim3(64), pad, st, ctx, out, shares, stride,
                          lam, n);
       HIP_TRY(hipGetLastError());
       return SCL_OK;
@@ -1098,18 +1062,11 @@ struct RecoverFixed {
   static int run(const typename F::Ctx& ctx, u64* out, const u64* shares, size_t stride, const Table<F>& lam, int m,
                  size_t npacks, hipStream_t st) {
     if (m == M) {
-      const bool wave_groups = g_stream_block.load() == 64;
-      const int blk = wave_groups ? 64 : BLOCK;
+      // single-wave workgroups under the residency cap (kernels.hpp, "Launch geometry")
       const long sw = g_stream_waves.load();
-      const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 1 ? 10 : 12) : sw, blk, 0);
-      const dim3 g(grid_for_block(npacks, blk));
-      if (!g_nontemporal.load())
-        hipLaunchKernelGGL((k_recover_fixed<F, VEC, M, false>), dim3(grid_for(npacks)), dim3(BLOCK), 0, st, ctx, out,
-                           shares, stride, lam, npacks);
-      else if (wave_groups)
-        hipLaunchKernelGGL((k_recover_fixed<F, VEC, M, true, 64>), g, dim3(64), pad, st, ctx, out, shares, stride, lam, npacks);
-      else
-        hipLaunchKernelGGL((k_recover_fixed<F, VEC, M, true>), g, dim3(BLOCK), pad, st, ctx, out, shares, stride, lam, npacks);
+      const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 1 ? 10 : 12) : sw, 64, 0);
+      hipLaunchKernelGGL((k_recover_fixed<F, VEC, M>), dim3(grid_for_block(npacks, 64)), dim3(64), pad, st, ctx, out, shares,
+                         stride, lam, npacks);
       return SCL_OK;
     }
     if constexpr (M > 1) return RecoverFixed<F, M - 1>::template run<VEC>(ctx, out, shares, stride, lam, m, npacks, st);
@@ -1269,8 +1226,8 @@ int ew_inverse(const typename F::Ctx& ctx, bool div, u64* dst, const u64* a, con
       LAUNCH_CHECK();
       if (n & 1) {  // the odd element out
         const size_t o = n - 1;
-        if (div) hipLaunchKernelGGL((k_ew<F, 5, 1, true>), dim3(1), dim3(BLOCK), 0, st, ctx, dst + o, a + o, b + o, (size_t)1, flag);
-        else hipLaunchKernelGGL((k_ew<F, 4, 1, true>), dim3(1), dim3(BLOCK), 0, st, ctx, dst + o, a + o, b, (size_t)1, flag);
+        if (div) hipLaunchKernelGGL((k_ew<F, 5, 1>), dim3(1), dim3(BLOCK), 0, st, ctx, dst + o, a + o, b + o, (size_t)1, flag);
+        else hipLaunchKernelGGL((k_ew<F, 4, 1>), dim3(1), dim3(BLOCK), 0, st, ctx, dst + o, a + o, b, (size_t)1, flag);
         LAUNCH_CHECK();
       }
       return SCL_OK;
@@ -1444,26 +1401,20 @@ int scl_hip_set_tuning(const char* key, long value) {
   if (!key) return fail(SCL_ERR_BAD_ARG, "key is NULL");
   const std::string k(key);
   if (k == "max_blocks") g_max_blocks = value;
-  else if (k == "nontemporal") g_nontemporal = value;
   else if (k == "force_scalar") g_force_scalar = value;
   else if (k == "force_table") g_force_table = value;
-  else if (k == "mfma_areg") g_mfma_areg = value;
   else if (k == "prg_two_pass") g_prg_two_pass = value;
-  else if (k == "mfma_pipe") g_mfma_pipe = value;
-  else if (k == "mfma_tpb") g_mfma_tpb = value;
   else if (k == "aes_blocks") g_aes_blocks = value;
   else if (k == "inv_batch") g_inv_batch = value;
   else if (k == "inv_two_level") g_inv_two_level = value;
   else if (k == "transpose_tile") g_transpose_tile = value;
   else if (k == "gemm_slab_mib") g_gemm_slab_mib = value;
   else if (k == "matmul_lds_min") g_matmul_lds_min = value;
-  else if (k == "stream_block") g_stream_block = (value == 256 ? 256 : 64);
   else if (k == "stream_waves") g_stream_waves = value;
   else if (k == "share_waves") g_share_waves = value;
   else if (k == "share_waves128") g_share_waves128 = value;
   else if (k == "mfma") g_mfma = value;
   else if (k == "gf_tiles") g_gf_tiles = value;
-  else if (k == "prg_t3") g_prg_t3 = value;
   else if (k == "open_gather_always") g_open_gather_always = value;
   else return fail(SCL_ERR_BAD_ARG, "unknown tuning key " + k);
   return SCL_OK;
@@ -1531,7 +1482,6 @@ static int ew_impl(int field, int op, uint64_t* dst, const uint64_t* a, const ui
       }
     }
     const int vec = vec_width<F>({dst, a, binary ? b : nullptr}, {});
-    const bool nt = g_nontemporal.load() != 0;
     const long batch = g_inv_batch.load();
     int rc_ = SCL_OK;
     constexpr bool is_field = F::TAG != 5 && F::TAG != 6;
@@ -1554,8 +1504,7 @@ static int ew_impl(int field, int op, uint64_t* dst, const uint64_t* a, const ui
         const dim3 g(grid_for(npacks)), blk(BLOCK);
 #define EW_CASE(OP)                                                                                             \
   case OP:                                                                                                      \
-    if (nt) hipLaunchKernelGGL((k_ew<F, OP, VEC, true>), g, blk, 0, S(stream), ctx, d, pa, pb, npacks, flag);   \
-    else hipLaunchKernelGGL((k_ew<F, OP, VEC, false>), g, blk, 0, S(stream), ctx, d, pa, pb, npacks, flag);     \
+    hipLaunchKernelGGL((k_ew<F, OP, VEC>), g, blk, 0, S(stream), ctx, d, pa, pb, npacks, flag);                 \
     break;
         switch (op) {
           EW_CASE(0) EW_CASE(1) EW_CASE(2) EW_CASE(3) EW_CASE(4) EW_CASE(5)
@@ -1612,7 +1561,7 @@ int scl_hip_scalar_mul(int field, uint64_t* dst, const uint64_t* a, const uint64
     }
     return split_vec<F>(vec, n, [&](auto V, size_t first, size_t npacks) -> int {
       constexpr int VEC = decltype(V)::value;
-      hipLaunchKernelGGL((k_scalar_mul<F, VEC, true>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx,
+      hipLaunchKernelGGL((k_scalar_mul<F, VEC>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx,
                          dst + first * F::LIMBS, a + first * F::LIMBS, sc, npacks);
       LAUNCH_CHECK();
       return SCL_OK;
@@ -1872,7 +1821,6 @@ static int recover_block(int field, uint64_t* out, const uint64_t* shares, size_
     using F = decltype(f);
     SCL_TRY(check_align<F>({out, shares}));
     const int vec = vec_width<F>({out, shares}, {stride});
-    const bool nt = g_nontemporal.load() != 0;
     const bool fixed = (m <= FIXED_M_MAX) && (F::TAG <= 1) && !g_force_table.load() && !prev;
     if (m > (size_t)BigTable<F>::CAP) return fail(SCL_ERR_BAD_ARG, "recover: internal party block too large");
     Table<F> lam;
@@ -1916,12 +1864,9 @@ static int recover_block(int field, uint64_t* out, const uint64_t* shares, size_
         if constexpr (F::TAG <= 1) {
           SCL_TRY((RecoverFixed<F, FIXED_M_MAX>::template run<VEC>(ctx, o, sh, stride, lam, (int)m, npacks, S(stream))));
         }
-      } else if (nt) {
-        hipLaunchKernelGGL((k_recover_table<F, VEC, true>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx, o,
-                           sh, stride, big, (int)m, npacks, prev ? prev + first * F::LIMBS : nullptr);
       } else {
-        hipLaunchKernelGGL((k_recover_table<F, VEC, false>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx, o,
-                           sh, stride, big, (int)m, npacks, prev ? prev + first * F::LIMBS : nullptr);
+        hipLaunchKernelGGL((k_recover_table<F, VEC>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx, o, sh, stride,
+                           big, (int)m, npacks, prev ? prev + first * F::LIMBS : nullptr);
       }
       LAUNCH_CHECK();
       return SCL_OK;
@@ -1990,19 +1935,19 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
         return split_vec<F>(vec, N, [&](auto V, size_t first, size_t npacks) -> int {
           constexpr int VEC = decltype(V)::value;
           // The Mersenne fields: single-wave workgroups under the residency cap, threshold compiled in (k_share_small_t);
-          // "share_waves" 0 or "stream_block" 256 give the 256-thread kernel with the threshold at run time
+          // "share_waves" 0 gives the 256-thread kernel with the threshold at run time
           const long sw = g_share_waves.load();
           bool launched = false;
           // (Mersenne127: 12 resident waves per CU, 0.39 -> 0.37 ms at C3's size and steadier; Mont128 -- the Barrett fold --
           // the same kernel since round 4, "share_waves128" = the cap of the 16-byte fields, 0 = the 256-thread kernel)
           if constexpr (F::TAG <= 2) {
             const long sw128 = g_share_waves128.load();
-            if (sw > 0 && g_stream_block.load() == 64 && (F::LIMBS == 1 || sw128 > 0)) {
+            if (sw > 0 && (F::LIMBS == 1 || sw128 > 0)) {
               const size_t pad = residency_pad(F::LIMBS == 1 ? sw : sw128, 64, sizeof(u32) * SmallVdm::CAP);
               const dim3 g(grid_for_block(npacks, 64));
 #define SST_CASE(TT)                                                                                                     \
   case TT:                                                                                                               \
-    hipLaunchKernelGGL((k_share_small_t<F, VEC, TT, 64>), g, dim3(64), pad, S(stream), ctx, shares + first * F::LIMBS, share_stride, \
+    hipLaunchKernelGGL((k_share_small_t<F, VEC, TT>), g, dim3(64), pad, S(stream), ctx, shares + first * F::LIMBS, share_stride, \
                        secrets + first * F::LIMBS, coeffs + first * F::LIMBS, coeff_stride, sv, (int)n, npacks);         \
     launched = true;                                                                                                     \
     break;
@@ -2017,13 +1962,13 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
             // 32-byte elements: a pair of lanes per secret (k_share_small_pair), single-wave workgroups under the 16-byte
             // fields' residency cap; "share_waves128" 0 = the lane-per-element kernel
             const long sw128 = g_share_waves128.load();
-            if (sw128 > 0 && g_stream_block.load() == 64) {
+            if (sw128 > 0) {
               // (the default cap of the 16-byte fields is 12; the lane pairs run best at 14-16: profiles/r5_probe_f3_waves.txt)
               const size_t pad = residency_pad(sw128 == 12 ? 16 : sw128, 64, sizeof(u32) * SmallVdm::CAP);
               const dim3 g(grid_for_block(2 * npacks, 64));
 #define SSP_CASE(TT)                                                                                                     \
   case TT:                                                                                                               \
-    hipLaunchKernelGGL((k_share_small_pair<F, TT, 64>), g, dim3(64), pad, S(stream), ctx, shares + first * F::LIMBS, share_stride, \
+    hipLaunchKernelGGL((k_share_small_pair<F, TT>), g, dim3(64), pad, S(stream), ctx, shares + first * F::LIMBS, share_stride, \
                        secrets + first * F::LIMBS, coeffs + first * F::LIMBS, coeff_stride, sv, (int)n, npacks);         \
     launched = true;                                                                                                     \
     break;
@@ -2249,7 +2194,7 @@ static int share_prg_impl(int field, uint64_t* shares, size_t share_stride, cons
         return split_vec<F>(vec, N, [&](auto V, size_t first, size_t npacks) -> int {
           constexpr int VEC = decltype(V)::value;
           const int nblk = F::LIMBS == 1 ? (int)(t / 2 + 1) : (int)t;
-          if (t == 3 && g_prg_t3.load() != 0) {  // BASELINE's threshold: the term loop compiled in ("prg_t3" 0: the generic kernel)
+          if (t == 3) {  // BASELINE's threshold: the term loop compiled in (profiles/r3_probe_prg_t3.txt)
             AES4_LAUNCH((k_share_prg_small_t<F, VEC, (F::LIMBS == 1 ? 2 : 3), 3>), npacks, S(stream), shares + first * F::LIMBS,
                         share_stride, secrets + first * F::LIMBS, key, (u64)(counter0 + first * blocks_per_secret), sv, (int)n,
                         npacks);
@@ -2597,15 +2542,10 @@ int scl_hip_additive_recover(int field, uint64_t* out, const uint64_t* shares, s
     using F = decltype(f);
     SCL_TRY(check_align<F>({out, shares}));
     const int vec = vec_width<F>({out, shares}, {stride});
-    const bool nt = g_nontemporal.load() != 0;
     return split_vec<F>(vec, N, [&](auto V, size_t first, size_t npacks) -> int {
       constexpr int VEC = decltype(V)::value;
-      if (nt)
-        hipLaunchKernelGGL((k_additive_recover<F, VEC, true>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx,
-                           out + first * F::LIMBS, shares + first * F::LIMBS, stride, (int)n, npacks);
-      else
-        hipLaunchKernelGGL((k_additive_recover<F, VEC, false>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx,
-                           out + first * F::LIMBS, shares + first * F::LIMBS, stride, (int)n, npacks);
+      hipLaunchKernelGGL((k_additive_recover<F, VEC>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx,
+                         out + first * F::LIMBS, shares + first * F::LIMBS, stride, (int)n, npacks);
       LAUNCH_CHECK();
       return SCL_OK;
     });

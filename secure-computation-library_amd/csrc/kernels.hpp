@@ -151,13 +151,13 @@ __device__ __forceinline__ void raise_flag(unsigned* flag) {
 }
 
 // Vector::add/subtract/multiplyEntryWise, FF::negate/invert/operator/ (vector.h:199-245, ff.h:203-246)
-template <class F, int OP, int VEC, bool NT>
+template <class F, int OP, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_ew(typename F::Ctx ctx, u64* dst, const u64* a, const u64* b,
                                               size_t npacks, unsigned* zero_flag) {
   SCL_GRID_STRIDE(q, npacks) {
     const size_t off = q * VEC * F::LIMBS;
-    Pack<F, VEC> x = load_pack<F, VEC, NT>(a + off), y, r;
-    if constexpr (OP == 0 || OP == 1 || OP == 2 || OP == 5) y = load_pack<F, VEC, NT>(b + off);
+    Pack<F, VEC> x = load_pack<F, VEC, true>(a + off), y, r;
+    if constexpr (OP == 0 || OP == 1 || OP == 2 || OP == 5) y = load_pack<F, VEC, true>(b + off);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
       if constexpr (OP == 0) r.v[v] = F::add(ctx, x.v[v], y.v[v]);
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(BLOCK) void k_ew(typename F::Ctx ctx, u64* dst, con
           if (bad) r.v[v] = F::zero();
       }
     }
-    store_pack<F, VEC, NT>(dst + off, r);
+    store_pack<F, VEC, true>(dst + off, r);
   }
 }
 
@@ -616,15 +616,15 @@ __global__ __launch_bounds__(BLK) void k_ew_inv_blocked(typename F::Ctx ctx, u64
 }
 
 // Vector::scalarMultiply (vector.h:274-301)
-template <class F, int VEC, bool NT>
+template <class F, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_scalar_mul(typename F::Ctx ctx, u64* dst, const u64* a,
                                                       Table<F> scalar, size_t npacks) {
   SCL_GRID_STRIDE(q, npacks) {
     const size_t off = q * VEC * F::LIMBS;
-    Pack<F, VEC> x = load_pack<F, VEC, NT>(a + off);
+    Pack<F, VEC> x = load_pack<F, VEC, true>(a + off);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) x.v[v] = F::mul(ctx, scalar.v[0], x.v[v]);
-    store_pack<F, VEC, NT>(dst + off, x);
+    store_pack<F, VEC, true>(dst + off, x);
   }
 }
 
@@ -757,19 +757,19 @@ __global__ __launch_bounds__(BLOCK) void k_count_diff_masked(unsigned long long*
 // all M loads issued before the first multiply.
 //
 // Launch geometry (tools/streambench.hip on plain allocations, profiles/r2_streambench_*.txt): SINGLE-WAVE workgroups
-// (BLK = 64) and at most 8 of them resident per CU -- the host passes a dynamic LDS size that nothing reads, only to cap
+// (64 threads) and at most 8 of them resident per CU -- the host passes a dynamic LDS size that nothing reads, only to cap
 // the residency.  Each resident wave keeps m + 1 DRAM streams open; with 32 waves per CU the streams evict each other's
 // open rows, with 8 the CU still has 80 KiB of loads in flight (enough for HBM latency) and the kernel gains 6-7 % on
 // every allocation tried (1.52 / 1.49 -> 1.41 / 1.40 ms at (10,3), 10^8 secrets); 4 waves per CU lose.  The same cap is
 // available to k_share_small ("share_waves"), where it only pays with n and t compiled in.
-template <class F, int VEC, int M, bool NT, int BLK = BLOCK>
-__global__ __launch_bounds__(BLK) void k_recover_fixed(typename F::Ctx ctx, u64* out, const u64* shares,
-                                                       size_t stride, Table<F> lam, size_t npacks) {
-  for (size_t q = (size_t)blockIdx.x * BLK + threadIdx.x; q < npacks; q += (size_t)gridDim.x * BLK) {
+template <class F, int VEC, int M>
+__global__ __launch_bounds__(64) void k_recover_fixed(typename F::Ctx ctx, u64* out, const u64* shares,
+                                                      size_t stride, Table<F> lam, size_t npacks) {
+  for (size_t q = (size_t)blockIdx.x * 64 + threadIdx.x; q < npacks; q += (size_t)gridDim.x * 64) {
     const size_t off = q * VEC * F::LIMBS;
     Pack<F, VEC> x[M];
 #pragma unroll
-    for (int i = 0; i < M; ++i) x[i] = load_pack<F, VEC, NT>(shares + (size_t)i * stride * F::LIMBS + off);
+    for (int i = 0; i < M; ++i) x[i] = load_pack<F, VEC, true>(shares + (size_t)i * stride * F::LIMBS + off);
     Pack<F, VEC> r;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
@@ -778,7 +778,7 @@ __global__ __launch_bounds__(BLK) void k_recover_fixed(typename F::Ctx ctx, u64*
       for (int i = 0; i < M; ++i) F::mac(ctx, acc, lam.v[i], x[i].v[v]);
       r.v[v] = F::acc_fold(ctx, acc);
     }
-    store_pack<F, VEC, NT>(out + off, r);
+    store_pack<F, VEC, true>(out + off, r);
   }
 }
 
@@ -795,21 +795,21 @@ struct SmallLam {
   u32 neg;             // bit i: lambda_i = p - v[i]
 };
 
-template <class F, int M, bool NT, int BLK>
-__global__ __launch_bounds__(BLK) void k_recover_small(typename F::Ctx ctx, u64* out, const u64* shares, size_t stride, SmallLam lam,
-                                                       size_t n) {
+template <class F, int M>
+__global__ __launch_bounds__(64) void k_recover_small(typename F::Ctx ctx, u64* out, const u64* shares, size_t stride, SmallLam lam,
+                                                      size_t n) {
   typedef typename F::E E;
   if constexpr (F::LIMBS == 4) {
     // 32-byte elements: a PAIR of lanes per secret, lane h of the pair holding limbs 2h, 2h + 1 -- a wave's loads and stores are
     // then 1 KiB of consecutive bytes each (a lane per element reads 16 bytes out of every 32 twice over), and the ten shares
     // cost a lane 40 registers instead of 80.  The limb sums are linear, so each lane accumulates its own four 32-bit columns;
     // the halves meet over DPP (quad_perm 1,0,3,2) before the two reductions, which both lanes run, each storing its half.
-    for (size_t q = (size_t)blockIdx.x * BLK + threadIdx.x; q < 2 * n; q += (size_t)gridDim.x * BLK) {
+    for (size_t q = (size_t)blockIdx.x * 64 + threadIdx.x; q < 2 * n; q += (size_t)gridDim.x * 64) {
       const int h = (int)(q & 1);
       const size_t off = (q >> 1) * 4 + 2 * h;
       u64x2 x[M];
 #pragma unroll
-      for (int i = 0; i < M; ++i) x[i] = ldg<NT>(reinterpret_cast<const u64x2*>(shares + (size_t)i * stride * 4 + off));
+      for (int i = 0; i < M; ++i) x[i] = ldg<true>(reinterpret_cast<const u64x2*>(shares + (size_t)i * stride * 4 + off));
       u64 pos[4] = {0, 0, 0, 0}, neg[4] = {0, 0, 0, 0};
 #pragma unroll
       for (int i = 0; i < M; ++i) {
@@ -840,14 +840,14 @@ __global__ __launch_bounds__(BLK) void k_recover_small(typename F::Ctx ctx, u64*
       u64x2 o;
       o.x = h ? r.w[2] : r.w[0];
       o.y = h ? r.w[3] : r.w[1];
-      stg<NT>(reinterpret_cast<u64x2*>(out + off), o);
+      stg<true>(reinterpret_cast<u64x2*>(out + off), o);
     }
   } else {
-    for (size_t q = (size_t)blockIdx.x * BLK + threadIdx.x; q < n; q += (size_t)gridDim.x * BLK) {
+    for (size_t q = (size_t)blockIdx.x * 64 + threadIdx.x; q < n; q += (size_t)gridDim.x * 64) {
       const size_t off = q * F::LIMBS;
       Pack<F, 1> x[M];
 #pragma unroll
-      for (int i = 0; i < M; ++i) x[i] = load_pack<F, 1, NT>(shares + (size_t)i * stride * F::LIMBS + off);
+      for (int i = 0; i < M; ++i) x[i] = load_pack<F, 1, true>(shares + (size_t)i * stride * F::LIMBS + off);
       typename F::SAcc pos, neg;
       F::sacc_zero(pos);
       F::sacc_zero(neg);
@@ -858,7 +858,7 @@ __global__ __launch_bounds__(BLK) void k_recover_small(typename F::Ctx ctx, u64*
       }
       Pack<F, 1> r;
       r.v[0] = F::sub(ctx, F::sacc_fold(ctx, pos, F::zero()), F::sacc_fold(ctx, neg, F::zero()));
-      store_pack<F, 1, NT>(out + off, r);
+      store_pack<F, 1, true>(out + off, r);
     }
   }
 }
@@ -866,7 +866,7 @@ __global__ __launch_bounds__(BLK) void k_recover_small(typename F::Ctx ctx, u64*
 // Any m <= BigTable::CAP: lambda staged in LDS, rows consumed 8 at a time.
 // prev != nullptr: out = prev + this block of parties' terms -- how more parties than one table holds are summed
 // over several launches (canonical partial sums add exactly)
-template <class F, int VEC, bool NT>
+template <class F, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_recover_table(typename F::Ctx ctx, u64* out, const u64* shares,
                                                          size_t stride, BigTable<F> tab, int m, size_t npacks,
                                                          const u64* prev) {
@@ -891,7 +891,7 @@ __global__ __launch_bounds__(BLOCK) void k_recover_table(typename F::Ctx ctx, u6
     for (; i + 8 <= m; i += 8) {
       Pack<F, VEC> x[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) x[j] = load_pack<F, VEC, NT>(shares + (size_t)(i + j) * stride * F::LIMBS + off);
+      for (int j = 0; j < 8; ++j) x[j] = load_pack<F, VEC, true>(shares + (size_t)(i + j) * stride * F::LIMBS + off);
       if (terms + 8 > F::ACC_TERMS) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -909,7 +909,7 @@ __global__ __launch_bounds__(BLOCK) void k_recover_table(typename F::Ctx ctx, u6
       terms += 8;
     }
     for (; i < m; ++i) {
-      const Pack<F, VEC> x = load_pack<F, VEC, NT>(shares + (size_t)i * stride * F::LIMBS + off);
+      const Pack<F, VEC> x = load_pack<F, VEC, true>(shares + (size_t)i * stride * F::LIMBS + off);
       if (terms + 1 > F::ACC_TERMS) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -926,7 +926,7 @@ __global__ __launch_bounds__(BLOCK) void k_recover_table(typename F::Ctx ctx, u6
     Pack<F, VEC> r;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) r.v[v] = F::add(ctx, run[v], F::acc_fold(ctx, acc[v]));
-    store_pack<F, VEC, NT>(out + off, r);
+    store_pack<F, VEC, true>(out + off, r);
   }
 }
 
@@ -1840,14 +1840,14 @@ __global__ __launch_bounds__(BLK) void k_share_small(typename F::Ctx ctx, u64* s
 // straight-line -- then the cap gains 2-3 % on allocations the kernel writes fast and 9 % on those it writes slowly
 // (2.00 -> 1.83 ms at (10,3), 10^8 secrets; profiles/r2_streambench_pitch_and_regions.txt).  Mersenne61 only: Mersenne127's
 // heavier fold wants the occupancy.
-template <class F, int VEC, int T, int BLK>
-__global__ __launch_bounds__(BLK) void k_share_small_t(typename F::Ctx ctx, u64* shares, size_t stride, const u64* secrets,
-                                                       const u64* coeffs, size_t cstride, SmallVdm tab, int n,
-                                                       size_t npacks) {
+template <class F, int VEC, int T>
+__global__ __launch_bounds__(64) void k_share_small_t(typename F::Ctx ctx, u64* shares, size_t stride, const u64* secrets,
+                                                      const u64* coeffs, size_t cstride, SmallVdm tab, int n,
+                                                      size_t npacks) {
   __shared__ u32 V[SmallVdm::CAP];
-  for (int i = threadIdx.x; i < n * (T + 1); i += BLK) V[i] = tab.v[i];
+  for (int i = threadIdx.x; i < n * (T + 1); i += 64) V[i] = tab.v[i];
   __syncthreads();
-  for (size_t q = (size_t)blockIdx.x * BLK + threadIdx.x; q < npacks; q += (size_t)gridDim.x * BLK) {
+  for (size_t q = (size_t)blockIdx.x * 64 + threadIdx.x; q < npacks; q += (size_t)gridDim.x * 64) {
     const size_t off = q * VEC * F::LIMBS;
     Pack<F, VEC> c[T + 1];
     c[0] = load_pack<F, VEC, true>(secrets + off);
@@ -1879,20 +1879,20 @@ __global__ __launch_bounds__(BLK) void k_share_small_t(typename F::Ctx ctx, u64*
 // each lane sums its own four 32-bit columns for both, the pair swaps columns over DPP so that lane 0 holds party i's eight and
 // lane 1 party i + 1's, each reduces ONE share (as many reductions as a lane per element does; a first form that had both lanes
 // reduce every share lost: 0.94 against 0.88 ms, profiles/r5_probe_secp_share_pair_no_gain.txt), and the halves swap back for the stores.
-template <class F, int T, int BLK>
-__global__ __launch_bounds__(BLK) void k_share_small_pair(typename F::Ctx ctx, u64* shares, size_t stride, const u64* secrets,
-                                                          const u64* coeffs, size_t cstride, SmallVdm tab, int n, size_t N) {
+template <class F, int T>
+__global__ __launch_bounds__(64) void k_share_small_pair(typename F::Ctx ctx, u64* shares, size_t stride, const u64* secrets,
+                                                         const u64* coeffs, size_t cstride, SmallVdm tab, int n, size_t N) {
   static_assert(F::LIMBS == 4, "lane pairs: 32-byte elements");
   typedef typename F::E E;
   __shared__ u32 V[SmallVdm::CAP];
-  for (int i = threadIdx.x; i < n * (T + 1); i += BLK) V[i] = tab.v[i];
+  for (int i = threadIdx.x; i < n * (T + 1); i += 64) V[i] = tab.v[i];
   __syncthreads();
   auto partner = [](u64 v) {
     const u32 lo = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)v, 0xB1, 0xF, 0xF, false);
     const u32 hi = (u32)__builtin_amdgcn_update_dpp(0, (int)(u32)(v >> 32), 0xB1, 0xF, 0xF, false);
     return ((u64)hi << 32) | lo;
   };
-  for (size_t q = (size_t)blockIdx.x * BLK + threadIdx.x; q < 2 * N; q += (size_t)gridDim.x * BLK) {
+  for (size_t q = (size_t)blockIdx.x * 64 + threadIdx.x; q < 2 * N; q += (size_t)gridDim.x * 64) {
     const int h = (int)(q & 1);
     const size_t off = (q >> 1) * 4 + 2 * h;
     const u64x2 s = ldg<true>(reinterpret_cast<const u64x2*>(secrets + off));
@@ -2773,7 +2773,7 @@ __global__ __launch_bounds__(ABLOCK) void k_additive_share_prg(typename F::Ctx c
 }
 
 // reconstruct = Vector::sum per secret (vector.h:261-267)
-template <class F, int VEC, bool NT>
+template <class F, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_additive_recover(typename F::Ctx ctx, u64* out, const u64* shares,
                                                             size_t stride, int n, size_t npacks) {
   SCL_GRID_STRIDE(q, npacks) {
@@ -2790,7 +2790,7 @@ __global__ __launch_bounds__(BLOCK) void k_additive_recover(typename F::Ctx ctx,
     for (; i + 4 <= n; i += 4) {
       Pack<F, VEC> x[4];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) x[j] = load_pack<F, VEC, NT>(shares + (size_t)(i + j) * stride * F::LIMBS + off);
+      for (int j = 0; j < 4; ++j) x[j] = load_pack<F, VEC, true>(shares + (size_t)(i + j) * stride * F::LIMBS + off);
       if (terms + 4 > F::ACC_TERMS) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -2806,7 +2806,7 @@ __global__ __launch_bounds__(BLOCK) void k_additive_recover(typename F::Ctx ctx,
       terms += 4;
     }
     for (; i < n; ++i) {
-      const Pack<F, VEC> x = load_pack<F, VEC, NT>(shares + (size_t)i * stride * F::LIMBS + off);
+      const Pack<F, VEC> x = load_pack<F, VEC, true>(shares + (size_t)i * stride * F::LIMBS + off);
       if (terms + 1 > F::ACC_TERMS) {
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
@@ -2822,7 +2822,7 @@ __global__ __launch_bounds__(BLOCK) void k_additive_recover(typename F::Ctx ctx,
     Pack<F, VEC> r;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) r.v[v] = F::add(ctx, run[v], F::acc_fold(ctx, acc[v]));
-    store_pack<F, VEC, NT>(out + off, r);
+    store_pack<F, VEC, true>(out + off, r);
   }
 }
 

@@ -139,6 +139,28 @@ def test_null_handles_are_an_error_not_a_crash(scl):
     assert lib.scl_hip_comm_destroy(null) == 0
 
 
+# scl_hip_set_tuning's keys at their documented defaults (scl_hip.h), and the keys it no longer has: each of those selected a
+# kernel form no input reaches, retired with it once its A/B run had lost
+TUNING_DEFAULTS = {"max_blocks": 0, "aes_blocks": 0, "force_scalar": 0, "force_table": 0, "stream_waves": -1, "share_waves": 9,
+                   "share_waves128": 12, "mfma": 0, "open_gather_always": 0, "gf_tiles": 1, "prg_two_pass": 0, "inv_batch": 0,
+                   "inv_two_level": 0, "matmul_lds_min": 0, "transpose_tile": 0, "gemm_slab_mib": 0}
+RETIRED_TUNING_KEYS = ["nontemporal", "stream_block", "mfma_pipe", "mfma_areg", "mfma_tpb", "prg_t3"]
+
+
+@pytest.mark.parametrize("key", RETIRED_TUNING_KEYS)
+def test_set_tuning_refuses_a_retired_key(scl, key):
+    with pytest.raises(scl.SclError) as e:
+        scl.set_tuning(key, 0)
+    assert e.value.status == scl.ERR_BAD_ARG
+    assert b"unknown tuning key " + key.encode() in scl.lib.scl_hip_last_error()
+
+
+def test_set_tuning_accepts_every_kept_key_at_its_default(scl):
+    assert len(TUNING_DEFAULTS) == 16
+    for key, value in TUNING_DEFAULTS.items():
+        scl.set_tuning(key, value)
+
+
 def test_batch_calls_fail_loudly_without_a_gpu(scl):
     import torch
     if torch.cuda.is_available():

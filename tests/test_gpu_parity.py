@@ -719,7 +719,7 @@ def test_share_on_matrix_cores_vs_oracle(scl, port, n, t, N):
 
 
 @pytest.mark.parametrize("f", [O.M61, O.M127])
-def test_recover_fixed_and_table_kernels_agree(scl, port, f):
+def test_recover_fixed_table_and_scalar_kernels_agree(scl, port, f):
     L = O.LIMBS[f]
     for m in (1, 2, 7, 8, 9, 15, 16, 17, 24, 33, 100, 128):
         N = 515
@@ -734,12 +734,10 @@ def test_recover_fixed_and_table_kernels_agree(scl, port, f):
         finally:
             scl.set_tuning("force_table", 0)
         scl.set_tuning("force_scalar", 1)
-        scl.set_tuning("nontemporal", 0)
         try:
             assert np.array_equal(host(scl, scl.shamir_recover(f, ds, lam)), want), m
         finally:
             scl.set_tuning("force_scalar", 0)
-            scl.set_tuning("nontemporal", 1)
 
 
 def test_worst_case_lazy_accumulation(scl, port):
@@ -1612,7 +1610,7 @@ def test_open_step_on_one_rank_rccl(scl, port):
         dist.destroy_process_group()
 
 
-def test_six_host_threads_on_their_own_streams(scl, port):
+def test_six_host_threads_with_their_own_knobs_and_streams(scl, port):
     """include/scl_hip.h, Conventions: "callable concurrently from several host threads on different streams"; the only mutable
     state is per thread (tuning knobs, the Mont128 modulus, scratch and temporary arenas, the last error) or behind a mutex
     (device table caches).  Since round 4 that state lives in ONE translation unit and is `extern thread_local` in the six
@@ -1624,8 +1622,8 @@ def test_six_host_threads_on_their_own_streams(scl, port):
     import threading
     jobs = [
         dict(f=O.M61, n=10, t=3, N=200_001, knobs={}),
-        dict(f=O.M61, n=128, t=42, N=4_097, knobs={"stream_block": 256}),
-        dict(f=O.M61, n=128, t=42, N=3_001, knobs={"nontemporal": 0}),
+        dict(f=O.M61, n=128, t=42, N=4_097, knobs={"force_scalar": 1}),
+        dict(f=O.M61, n=128, t=42, N=3_001, knobs={"max_blocks": 7}),
         dict(f=O.MONT128, n=10, t=3, N=50_001, knobs={}, prime=2 ** 128 - 159),
         dict(f=O.MONT128, n=7, t=2, N=40_001, knobs={"share_waves128": 0}, prime=2 ** 127 - 1),   # (below 2^127: the Vandermonde-row share kernel instead of the small-node one)
         dict(f=O.GF2_128, n=40, t=13, N=9_001, knobs={"gf_tiles": 0}),
@@ -1651,7 +1649,7 @@ def test_six_host_threads_on_their_own_streams(scl, port):
             assert "0 not invertible modulo prime" in str(ei.value)
             out.append(scl.lib.scl_hip_last_error())
         for k in job["knobs"]:
-            scl.set_tuning(k, {"stream_block": 64, "nontemporal": 1, "share_waves128": 12, "gf_tiles": 1}[k])
+            scl.set_tuning(k, {"force_scalar": 0, "max_blocks": 0, "share_waves128": 12, "gf_tiles": 1}[k])
         return out
 
     want = [run(job, b"thr%d" % i) for i, job in enumerate(jobs)]      # one after the other, main thread
@@ -2683,28 +2681,25 @@ def test_bench_configs_quoted_on_eight_gpus_rehearsal_on_one_device(scl, config,
     assert line["n_gpus"] == 2 and line["verified"] is True and check(line, r.detail), line
 
 
-@pytest.mark.parametrize("n,t,N", [(128, 42, 3 * 256 * 32 + 17), (97, 5, 2 * 256 * 32 + 31), (128, 48, 256 * 32 + 1), (100, 33, 4 * 256 * 32)])
-def test_share_matrix_core_pipeline_many_trips(scl, port, n, t, N):
-    """k_share_mfma_m61_p16 / k_share_mfma_m61_pipe with several trips per workgroup (the cross-block software pipeline: fetch two blocks ahead,
-    recode under the matrix instructions) and a ragged last block: bit-identical to the burst kernel, to the VALU kernels
-    and, on a sample of secrets, to the oracle's per-secret Horner."""
+@pytest.mark.parametrize("n,t,N", [(128, 42, 3 * 256 * 32 + 17), (97, 5, 2 * 256 * 32 + 31), (128, 48, 256 * 32 + 1), (100, 33, 4 * 256 * 32),
+                                   (64, 21, 3 * 256 * 128 + 17)])
+def test_share_matrix_core_kernel_by_shape_many_trips(scl, port, n, t, N):
+    """The matrix-core share kernel the shape selects -- k_share_mfma_m61_p16 (four row tiles, two k-steps),
+    k_share_mfma_m61_pipe<1> (four row tiles, one k-step) or k_share_mfma_m61 (up to two row tiles) -- with several trips per
+    workgroup (the cross-block software pipeline: fetch ahead, recode under the matrix instructions) and a ragged last block:
+    bit-identical to the VALU kernels and, on a sample of secrets, to the oracle's per-secret Horner."""
     f, L = O.M61, 1
     secrets = scl.vector_random(f, N, b"pipe-s")
     coeffs = scl.vector_random(f, t * N, b"pipe-c").reshape(t, N, L)
     outs = {}
-    for name, keys in (("p16", {"mfma": 1, "mfma_pipe": 2}), ("pipe", {"mfma": 1, "mfma_pipe": 1}),
-                       ("burst", {"mfma": 1, "mfma_pipe": 0}), ("valu", {"mfma": -1})):
-        for k, v in keys.items():
-            scl.set_tuning(k, v)
+    for name, mode in (("mfma", 1), ("valu", -1)):
+        scl.set_tuning("mfma", mode)
         try:
             outs[name] = scl.shamir_share(f, secrets, coeffs, n)
         finally:
             scl.set_tuning("mfma", 0)
-            scl.set_tuning("mfma_pipe", 2)
-    assert scl.equals(f, outs["pipe"], outs["burst"])
-    assert scl.equals(f, outs["pipe"], outs["valu"])
-    assert scl.equals(f, outs["pipe"], outs["p16"])
-    hs, hc, got = host(scl, secrets), host(scl, coeffs), host(scl, outs["pipe"])
+    assert scl.equals(f, outs["mfma"], outs["valu"])
+    hs, hc, got = host(scl, secrets), host(scl, coeffs), host(scl, outs["mfma"])
     idx = sorted(set([0, 1, 31, 32, 33, 8191, 8192, N - 33, N - 2, N - 1] + list(range(N // 2, N // 2 + 40))))
     sub_s = hs[idx]
     sub_c = np.ascontiguousarray(np.transpose(hc[:, idx], (1, 0, 2)))

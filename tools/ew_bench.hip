@@ -122,8 +122,8 @@ static void run_field(const char* name, typename F::Ctx ctx, size_t n) {
   for (int div = 0; div < 2; ++div) {
     CK(hipMemset(flag, 0, 4));
     double base;
-    if (div) base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 5, VEC, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, npacks, flag); }, 2);
-    else base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 4, VEC, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, npacks, flag); }, 2);
+    if (div) base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 5, VEC>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, npacks, flag); }, 2);
+    else base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 4, VEC>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, npacks, flag); }, 2);
     std::printf("%-8s %s per-element  %8.3f ms  %7.2f G/s  %6.0f GB/s\n", name, div ? "div" : "inv", base, n / base / 1e6, (div ? 3 : 2) * E * n / base / 1e6);
     if (div) {
       run_batch<F, true, VEC, 4>(name, ctx, out, ref, a, b, n, flag, base);
@@ -210,13 +210,13 @@ static void run_field_rolled(const char* name, typename F::Ctx ctx, size_t n) {
   CK(hipDeviceSynchronize());
   const unsigned g = (unsigned)((n + BLOCK - 1) / BLOCK);
   typedef FieldArith<F> A;
-  double base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 4, 1, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
+  double base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 4, 1>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
   run_rolled<F, A, false, 16, 256>(name, ctx, out, ref, a, b, n, flag, base);
   run_rolled<F, A, false, 32, 256>(name, ctx, out, ref, a, b, n, flag, base);
   run_rolled<F, A, false, 64, 256>(name, ctx, out, ref, a, b, n, flag, base);
   run_rolled<F, A, false, 128, 256>(name, ctx, out, ref, a, b, n, flag, base);
   run_rolled<F, A, false, 64, 64>(name, ctx, out, ref, a, b, n, flag, base);
-  base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 5, 1, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
+  base = time_ms([&] { hipLaunchKernelGGL((k_ew<F, 5, 1>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
   run_rolled<F, A, true, 32, 256>(name, ctx, out, ref, a, b, n, flag, base);
   run_rolled<F, A, true, 64, 256>(name, ctx, out, ref, a, b, n, flag, base);
   CK(hipFree(a)); CK(hipFree(b)); CK(hipFree(ref)); CK(hipFree(out)); CK(hipFree(flag));
@@ -269,7 +269,7 @@ static void run_gf_all(size_t n) {
   CK(hipDeviceSynchronize());
   const unsigned g = (unsigned)((n + BLOCK - 1) / BLOCK);
   const Gf128::Ctx ctx{};
-  double base = time_ms([&] { hipLaunchKernelGGL((k_ew<Gf128, 2, 1, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 2);
+  double base = time_ms([&] { hipLaunchKernelGGL((k_ew<Gf128, 2, 1>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 2);
   std::printf("gf2_128  mul registers  %8.3f ms  %7.2f G/s  %6.0f GB/s\n", base, n / base / 1e6, 48.0 * n / base / 1e6);
   run_gf_mul<64>(out, ref, a, b, n, base);
   run_gf_mul<128>(out, ref, a, b, n, base);
@@ -282,7 +282,7 @@ static void run_gf_all(size_t n) {
   double ladder = time_ms([&] { hipLaunchKernelGGL(k_gf_inv_ladder, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, 0, out, a, nl); }, 1);
   std::printf("gf2_128  inv ladder of round 4 (254 register products), %zu elements  %8.3f ms  %7.4f G/s\n", nl, ladder, nl / ladder / 1e6);
   ladder *= 16.0;
-  base = time_ms([&] { hipLaunchKernelGGL((k_ew<Gf128, 4, 1, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
+  base = time_ms([&] { hipLaunchKernelGGL((k_ew<Gf128, 4, 1>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
   std::printf("gf2_128  inv Itoh-Tsujii per element, register products  %8.3f ms  %7.3f G/s  x%.1f vs the ladder\n", base, n / base / 1e6, ladder / base);
   std::printf("(below: x vs the ladder)\n");
   run_rolled<Gf128, GfLdsArith<64>, false, 1, 64>("gf2_128", ctx, out, ref, a, b, n, flag, ladder);
@@ -294,7 +294,7 @@ static void run_gf_all(size_t n) {
   std::printf("(window bits 3)\n");
   run_rolled<Gf128, GfLdsArith<64, 3>, false, 32, 64>("gf2_128", ctx, out, ref, a, b, n, flag, ladder);
   run_rolled<Gf128, GfLdsArith<256, 3>, false, 32, 256>("gf2_128", ctx, out, ref, a, b, n, flag, ladder);
-  base = time_ms([&] { hipLaunchKernelGGL((k_ew<Gf128, 5, 1, true>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
+  base = time_ms([&] { hipLaunchKernelGGL((k_ew<Gf128, 5, 1>), dim3(g), dim3(BLOCK), 0, 0, ctx, ref, a, b, n, flag); }, 1);
   std::printf("gf2_128  div per element (Itoh-Tsujii, register products)  %8.3f ms  %7.3f G/s\n", base, n / base / 1e6);
   run_rolled<Gf128, GfLdsArith<64>, true, 32, 64>("gf2_128", ctx, out, ref, a, b, n, flag, base);
   run_rolled<Gf128, GfLdsArith<64>, true, 64, 64>("gf2_128", ctx, out, ref, a, b, n, flag, base);

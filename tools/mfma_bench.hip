@@ -99,8 +99,8 @@ int main(int argc, char** argv) {
     std::printf("%-28s %8.3f ms  %6.2f G secrets/s  %6.0f GB/s\n", name, ms, N / ms / 1e6, (double)(t + 1 + n) * 8 * N / ms / 1e6);
   };
   {
-    const size_t shmem = mf_b_bytes(KS, MT);
-    auto kern = &k_share_mfma_m61<KS, MT, true, 512>;
+    const size_t shmem = mf_a_bytes(KS, MT) + mf_b_bytes(KS, MT);
+    auto kern = &k_share_mfma_m61<KS, MT>;
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     const size_t nblocks = (N + 63) / 64;
     const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);

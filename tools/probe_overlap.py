@@ -45,11 +45,11 @@ def both():
     for k in range(CH):
         with torch.cuda.stream(s1): aes(k)
         with torch.cuda.stream(s2): share_chunk(k)
-for knobs in ({}, {"stream_waves": 0}, {"stream_waves": 0, "stream_block": 256}, {"stream_waves": 4}, {"stream_waves": 6}):
+for knobs in ({}, {"stream_waves": 0}, {"stream_waves": 4}, {"stream_waves": 6}):
     for k_, v_ in knobs.items(): scl.set_tuning(k_, v_)
     a, b, c = wall(only_aes), wall(only_share), wall(both)
     print(knobs, f"AES only {a:.3f} | share only {b:.3f} | both {c:.3f} (sum {a + b:.3f})")
-scl.set_tuning("stream_waves", -1); scl.set_tuning("stream_block", 64)
+scl.set_tuning("stream_waves", -1)
 a, b, c = wall(only_aes), wall(only_share), wall(both)
 print(f"(10,3) Mersenne61, 10^8 secrets in {CH} chunks: AES only ({CH * nb} blocks) {a:.3f} ms | share only {b:.3f} ms | both, two streams {c:.3f} ms (sum {a + b:.3f}, max {max(a, b):.3f})")
 whole = wall(lambda: scl.shamir_share_prg(f, secrets, t, n, b"overlap", out=shares))

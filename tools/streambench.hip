@@ -256,9 +256,9 @@ int main(int argc, char** argv) {
   };
   const double sb = 112.0 * N, rb = 88.0 * N;
   {
-    const unsigned g = (unsigned)((npacks + 255) / 256);
+    const unsigned g = (unsigned)((npacks + 255) / 256), g64 = (unsigned)((npacks + 63) / 64);
     hipLaunchKernelGGL((k_share_small<M61, 2>), dim3(g), dim3(256), 0, 0, M61::Ctx{}, ref_sh, N, secrets[0], coeffs[0], N, sv, TT, NP, npacks);
-    hipLaunchKernelGGL((k_recover_fixed<M61, 2, NP, true>), dim3(g), dim3(256), 0, 0, M61::Ctx{}, ref_out, ref_sh, N, lamt, npacks);
+    hipLaunchKernelGGL((k_recover_fixed<M61, 2, NP>), dim3(g64), dim3(64), 0, 0, M61::Ctx{}, ref_out, ref_sh, N, lamt, npacks);
     CK(hipDeviceSynchronize());
     std::printf("reference round trip: diff %zu\n", diff(ref_out, secrets[0], N));
   }
@@ -289,11 +289,11 @@ int main(int argc, char** argv) {
     SHR2(256, true, 1, 0) SHR2(64, true, 1, 19 * 1024)
 #undef SHR2
     {
-      const unsigned g = (unsigned)((npacks + 255) / 256);
+      const unsigned g64 = (unsigned)((npacks + 63) / 64);
       float ms[2];
       for (int a = 0; a < 2; ++a)
-        ms[a] = time_it([&] { hipLaunchKernelGGL((k_recover_fixed<M61, 2, NP, true>), dim3(g), dim3(256), 0, 0, M61::Ctx{}, out[a], shares[a], N, lamt, npacks); }, 10);
-      report("recover", "library k_recover_fixed b256", ms[0], ms[1], rb, diff(ref_out, out[0], N) + diff(ref_out, out[1], N));
+        ms[a] = time_it([&] { hipLaunchKernelGGL((k_recover_fixed<M61, 2, NP>), dim3(g64), dim3(64), 19456, 0, M61::Ctx{}, out[a], shares[a], N, lamt, npacks); }, 10);
+      report("recover", "library k_recover_fixed b64 lds 19456 B", ms[0], ms[1], rb, diff(ref_out, out[0], N) + diff(ref_out, out[1], N));
     }
 #define REC1(BLK, LDSB)                                                                                             \
   {                                                                                                                 \
@@ -332,7 +332,7 @@ int main(int argc, char** argv) {
       float ms_s[2], ms_r[2];
       for (int a = 0; a < 2; ++a) {
         ms_s[a] = time_it([&] { hipLaunchKernelGGL((k_share_small<M61, 2>), dim3(g), dim3(256), 0, 0, M61::Ctx{}, pitched[a], pitch, secrets[a], coeffs[a], N, sv, TT, NP, npacks); }, 10);
-        ms_r[a] = time_it([&] { hipLaunchKernelGGL((k_recover_fixed<M61, 2, NP, true, 64>), dim3(g64), dim3(64), 19456, 0, M61::Ctx{}, out[a], pitched[a], pitch, lamt, npacks); }, 10);
+        ms_r[a] = time_it([&] { hipLaunchKernelGGL((k_recover_fixed<M61, 2, NP>), dim3(g64), dim3(64), 19456, 0, M61::Ctx{}, out[a], pitched[a], pitch, lamt, npacks); }, 10);
       }
       std::printf("pitch N + %9zu B: share %7.3f / %7.3f ms  recover(b64, 8 waves/CU) %7.3f / %7.3f ms  diff %zu\n", pad_bytes, ms_s[0], ms_s[1],
                   ms_r[0], ms_r[1], diff(ref_out, out[0], N) + diff(ref_out, out[1], N));

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Launch-geometry sweep for the streaming kernels (run on the GPU box).
-Prints GB/s (algorithmic bytes) per (max_blocks, nontemporal) for recover, share and the copy probe."""
+Prints GB/s (algorithmic bytes) per max_blocks for recover, share and the copy probe."""
 import os
 import sys
 
@@ -36,13 +36,11 @@ def timeit(fn, reps=10):
 half = (shares.numel() // 2) & ~1
 src, dst = shares.view(-1)[:half], shares.view(-1)[half:2 * half]
 print(f"field={scl.field_name(f)} n={n} t={t} N={N}")
-print(f"{'max_blocks':>10s} {'nt':>3s} {'recover GB/s':>13s} {'share GB/s':>11s} {'copy GB/s':>10s}")
-for nt in (1, 0):
-    scl.set_tuning("nontemporal", nt)
-    for mb in (512, 1024, 2048, 4096, 8192, 16384, 65536, 1 << 30):
-        scl.set_tuning("max_blocks", mb)
-        r = timeit(lambda: scl.shamir_recover(f, shares, lam, out=out))
-        s = timeit(lambda: scl.shamir_share(f, secrets, coeffs, n, out=shares))
-        c = timeit(lambda: scl.stream_copy(dst, src))
-        print(f"{mb:>10d} {nt:>3d} {(n + 1) * E * N / r / 1e6:13.0f} {((1 + t) + n) * E * N / s / 1e6:11.0f} "
-              f"{2 * half * 8 / c / 1e6:10.0f}")
+print(f"{'max_blocks':>10s} {'recover GB/s':>13s} {'share GB/s':>11s} {'copy GB/s':>10s}")
+for mb in (512, 1024, 2048, 4096, 8192, 16384, 65536, 1 << 30):
+    scl.set_tuning("max_blocks", mb)
+    r = timeit(lambda: scl.shamir_recover(f, shares, lam, out=out))
+    s = timeit(lambda: scl.shamir_share(f, secrets, coeffs, n, out=shares))
+    c = timeit(lambda: scl.stream_copy(dst, src))
+    print(f"{mb:>10d} {(n + 1) * E * N / r / 1e6:13.0f} {((1 + t) + n) * E * N / s / 1e6:11.0f} {2 * half * 8 / c / 1e6:10.0f}")
+scl.set_tuning("max_blocks", 0)
