@@ -18,6 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))     # oracle_lib: the oracle is 
 import torch  # noqa: E402
 import scl_amd as scl  # noqa: E402
 import oracle_lib as O  # noqa: E402
+import extremes as X  # noqa: E402
 
 FIELDS = [scl.M61, scl.M127, scl.MONT128, scl.GF2_128, scl.SECP256K1_SCALAR, scl.SECP256K1_FIELD]
 EDGES = [0, 1, 2, 3, 63, 64, 65, 127, 255, 256, 257, 511, 512, 513, 1023, 1025, 4095, 4096, 4097, 8191, 8193, 16385, 65537]
@@ -42,6 +43,7 @@ def main():
     rng = np.random.default_rng(seed0)
     t_end = time.time() + budget
     runs, bad, by_kind, secs, by_knob = 0, 0, {}, {}, {}
+    extreme, n_extreme = False, 0
 
     def size(cap):
         r = rng.random()
@@ -50,7 +52,12 @@ def main():
         return int(rng.integers(0, cap + 1))
 
     def rand(f, n, tag):
-        return port.vector_random(f, b"fuzz-%d-%s" % (runs, tag), n) if n else np.zeros((0, scl.limbs(f)), dtype=np.uint64)
+        a = port.vector_random(f, b"fuzz-%d-%s" % (runs, tag), n) if n else np.zeros((0, scl.limbs(f)), dtype=np.uint64)
+        if extreme and n:   # the operands that reach the kernels' accumulator bounds, at random places in the array
+            vals = X.pool(f)
+            pick = rng.random(n) < 0.5
+            a[pick] = X.Model(f).arr([vals[i] for i in rng.integers(0, len(vals), int(pick.sum()))])
+        return a
 
     def dev(a):
         a = np.ascontiguousarray(a)
@@ -80,6 +87,10 @@ def main():
         kind = KINDS[rng.integers(len(KINDS))]
         by_kind[kind] = by_kind.get(kind, 0) + 1
         t_case = time.time()
+        # one case in four draws its operand arrays half from the pool of extreme operands (tests/extremes.py); not the Vandermonde
+        # case, whose random nodes must stay distinct
+        extreme = rng.random() < 0.25 and kind != "vdm"
+        n_extreme += extreme
         # one case in three runs with a tuning knob off its default: the alternative kernels and launch geometries behind every
         # entry point (the knobs pin paths for A/B runs; none of them may change a result)
         knob = None
@@ -453,7 +464,7 @@ def main():
     sys.path.insert(0, ROOT)
     from bench_legs.pmc import kernel_source_hash     # one campaign per change of the kernel sources: the line says which
     print(f"fuzz_abi: kernel sources {kernel_source_hash()}, seed {seed0}")
-    print(f"fuzz_abi: {runs} cases in {budget:g} s, {bad} mismatches; by kind {by_kind}; seconds by kind { {k: round(v, 1) for k, v in secs.items()} }; cases by knob {by_knob}", flush=True)
+    print(f"fuzz_abi: {runs} cases in {budget:g} s, {bad} mismatches; {n_extreme} cases on extreme operands; by kind {by_kind}; seconds by kind { {k: round(v, 1) for k, v in secs.items()} }; cases by knob {by_knob}", flush=True)
     return 1 if bad else 0
 
 

@@ -141,3 +141,17 @@ def test_gf2_128_host_arithmetic_against_a_bit_serial_multiplier(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout
 
+
+
+def test_lazy_accumulators_at_their_term_bounds(tmp_path):
+    """Every field's lazy accumulator of detail/field.hpp -- mac / acc_add / acc_fold at exactly F::ACC_TERMS terms (2^24 where
+    the bound is 2^30), kmac / kacc_fold at F::K_TERMS with the largest words the prepared-constant form accepts -- driven with
+    p - 1, all-ones limbs and the digit-extreme Mersenne61 words, against double-and-add on the field's reduced add; and the
+    muladd_small_lazy steps of Mersenne61 and Mersenne127 chained at the edges of their stated input ranges
+    (tests/cxx/lazy_acc_check.cc).  The kernels compile the same functions; tests/test_gpu_extremes.py drives them there."""
+    exe = str(tmp_path / "lazy_acc_check")
+    b = subprocess.run(["g++", "-std=c++20", "-O2", "-w", f"-I{ROOT}/include", "-o", exe, os.path.join(CXX, "lazy_acc_check.cc")],
+                       capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout + r.stderr

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from extremes import gf_inv, gf_mul  # the shift-xor model, shared with the extreme-operand tests
 
 R = 1 << 128
 MASK = R - 1
@@ -147,30 +148,6 @@ def test_oracle_mont128_against_python_big_integers(port, p):
 
 
 # ---- GF(2^128) --------------------------------------------------------------------------------------------------
-def gf_mul(a: int, b: int) -> int:
-    """bit-serial: for each set bit of b add a * x^i, a * x reduced by x^128 = x^7 + x^2 + x + 1 (0x87)"""
-    r = 0
-    while b:
-        if b & 1:
-            r ^= a
-        b >>= 1
-        a <<= 1
-        if a >> 128:
-            a = (a & MASK) ^ 0x87
-    return r
-
-
-def gf_inv(a: int) -> int:
-    """a^(2^128 - 2) by square-and-multiply on the bit-serial multiplier"""
-    r, e, base = 1, (1 << 128) - 2, a
-    while e:
-        if e & 1:
-            r = gf_mul(r, base)
-        base = gf_mul(base, base)
-        e >>= 1
-    return r
-
-
 def gf_vectors(n: int = 120):
     rng = random.Random(0x6F2128)
     xs = [0, 1, 2, MASK, 1 << 127, 0x87, (1 << 127) | 1, 3]
