@@ -322,6 +322,62 @@ int scl_hip_frame_unpack(int field, uint64_t* dst_dev, size_t capacity, const un
 /* plain device copy kernel (16 B per lane) used to measure achievable HBM bandwidth */
 int scl_hip_stream_copy(void* dst_dev, const void* src_dev, size_t bytes, void* stream);
 
+/* ---- commitments: scl::util::Sha256 and scl::util::MerkleTree<Sha256, LEAF> ------------------------------------
+ * A digest is 32 bytes; digest buffers are 16-byte aligned.  Everything here is asynchronous on `stream` and reads nothing back
+ * to the host; leaves, build, paths and verify launch kernels and nothing else, so a chain of them can be captured into a
+ * hipGraph (scl_hip_merkle_root takes the calling thread's temporary arena and its event, like the other arena calls).  (The reference's default util::Hash<256> is its Sha3, whose absorb loop
+ * does not compute SHA-3 -- DESIGN.md section 9; only Sha256 is built.)
+ *
+ * Batched Sha256{}.update(msg, msg_len).finalize() (include/scl/util/sha256.h:33-67, iuf_hash.h:41-105,
+ * src/scl/util/sha256.cc): message i is the msg_len bytes at msgs_dev + i * msg_stride (any length, any alignment;
+ * msg_stride >= msg_len), digest i goes to digests_dev + i * 32. */
+int scl_hip_sha256(unsigned char* digests_dev, const unsigned char* msgs_dev, size_t msg_len, size_t msg_stride,
+                   size_t count, void* stream);
+/* MerkleTree::hashLeafs without its padding (include/scl/util/merkle.h:74-92): digest = Sha256 of the element's
+ * Serializer<FF>::write image (ff.h:355-391) -- the bytes scl_hip_wire_pack puts behind its count word.  a_dev is a
+ * rows x cols window of elements with a row pitch of `stride` elements; the digest of element (row, col) goes to
+ * digests_dev + (row * cols + col) * 32.  A share matrix [party][secret] passed whole (rows = n, cols = N) is therefore the
+ * leaf level of N trees of n leaves in the layout below.  Ring tags are refused (no Serializer<Z2k> in the reference). */
+int scl_hip_merkle_leaves(int field, unsigned char* digests_dev, const uint64_t* a_dev, size_t stride, size_t rows,
+                          size_t cols, void* stream);
+/* The shape of the reference's tree over L leaves (merkle.h:85-89,110-116: the leaf level and every later level of odd size
+ * greater than one repeat their last digest; one leaf hashes with itself).  Host only.  depth = hashing levels =
+ * max(1, ceil(log2 L)); level_size(L, 0) = L, level_size(L, l + 1) = ceil(level_size(L, l) / 2) down to 1 at l = depth and
+ * 0 beyond; tree_bytes = 32 * T * the sum of all level sizes.  L = 0: all three return 0. */
+size_t scl_hip_merkle_depth(size_t L);
+size_t scl_hip_merkle_level_size(size_t L, size_t level);
+size_t scl_hip_merkle_tree_bytes(size_t L, size_t T);
+/* MerkleTree::hash (merkle.h:94-120) for T trees of L leaves at once, keeping every level.  Layout, leaf-major and
+ * tree-minor: node j of tree tau at level l lives at tree_dev + level_offset(l) + (j * T + tau) * 32, level_offset(0) = 0,
+ * level_offset(l + 1) = level_offset(l) + level_size(L, l) * T * 32; the T roots are the last T * 32 bytes.
+ * leaf_digests_dev holds level 0 in the same layout and is copied in; it may BE tree_dev (no copy), not overlap otherwise.
+ * L = 0 or T = 0: SCL_ERR_BAD_ARG (the reference reads digests[0] of an empty vector). */
+int scl_hip_merkle_build(unsigned char* tree_dev, const unsigned char* leaf_digests_dev, size_t L, size_t T, void* stream);
+/* The same reduction keeping nothing but the roots: roots_dev[tau * 32 ..]; the levels in between live in the calling
+ * thread's temporary arena (two levels' worth: 24 * T * L bytes at most). */
+int scl_hip_merkle_root(unsigned char* roots_dev, const unsigned char* leaf_digests_dev, size_t L, size_t T, void* stream);
+/* MerkleTree::prove (merkle.h:122-162) for k queries against a built batch: path_dev[(l * k + q) * 32 ..] = the sibling
+ * of query q's node at level l < depth (the node itself where the reference repeats it).  Query q asks for leaf
+ * leaf_index_dev[q] of tree tree_index_dev[q] (64-bit indices in device memory; values out of range are clamped to L - 1 /
+ * T - 1 before use -- such a path does not verify under the index that was asked for).  A NULL array selects the regular
+ * pattern, leaf-major and tree-minor like the nodes: tree = q mod T, leaf = first_leaf + q / T -- so (T = 1, first_leaf = 0,
+ * k = L) is every leaf of one tree and (k = T, first_leaf = p) is party p's leaf in every tree.  first_leaf is ignored when
+ * leaf_index_dev is given; a regular pattern that reaches a leaf >= L is SCL_ERR_INVALID_RANGE.  The reference's
+ * direction[l] is bit l of the leaf index (merkle.h:140-148), so its Bitmap is the index's low `depth` bits, little-endian
+ * bytes (bitmap.h:88-103): the index is the proof's second half and is not written here. */
+int scl_hip_merkle_paths(unsigned char* path_dev, const unsigned char* tree_dev, size_t L, size_t T,
+                         const uint64_t* leaf_index_dev, const uint64_t* tree_index_dev, size_t first_leaf, size_t k,
+                         void* stream);
+/* MerkleTree::verify (merkle.h:165-181) for k queries: ok_dev[q] = 1 iff walking path_dev[(l * k + q) * 32 ..], l < depth,
+ * up from leaf_digests_dev[q * 32 ..] with the directions of the leaf index arrives at the root, else 0.  The leaf index of
+ * query q is leaf_index_dev[q], or `leaf` for every query when that is NULL; its root is roots_dev[root_index_dev[q] * 32 ..],
+ * or root q mod num_roots when that is NULL.  A device index out of range (leaf >= 2^depth, root >= num_roots) is
+ * masked / clamped and the query's byte is 0; `leaf` >= 2^depth from the host is SCL_ERR_INVALID_RANGE.  Never faults on a
+ * bad proof, and no lane leaves early on its data. */
+int scl_hip_merkle_verify(unsigned char* ok_dev, const unsigned char* leaf_digests_dev, const uint64_t* leaf_index_dev,
+                          size_t leaf, const unsigned char* path_dev, size_t depth, const unsigned char* roots_dev,
+                          const uint64_t* root_index_dev, size_t num_roots, size_t k, void* stream);
+
 /* ---- the open step: every party sends its shares to every party, then reconstructs ----------------------------
  * Replaces Network::send to each party + Network::recv from each party (include/scl/net/network.h:148-152,178-185; the
  * pattern of test/scl/protocol/beaver.h:43-55) followed by shamirRecoverP per secret (shamir.h:81-104), for a whole

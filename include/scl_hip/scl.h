@@ -4,6 +4,7 @@
 
 #include "hip/device.h"
 #include "hip/elementwise.h"
+#include "hip/merkle.h"
 #include "hip/open.h"
 #include "math/fields/ff_ops.h"
 #include "math/ff.h"
@@ -16,7 +17,13 @@
 #include "serialization/serializer.h"
 #include "ss/additive.h"
 #include "ss/shamir.h"
+#include "util/bitmap.h"
+#include "util/digest.h"
+#include "util/iuf_hash.h"
+#include "util/merkle.h"
+#include "util/merkle_proof.h"
 #include "util/prg.h"
+#include "util/sha256.h"
 #include "names.h"
 
 #endif

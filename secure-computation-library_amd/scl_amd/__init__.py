@@ -577,6 +577,117 @@ def frame_unpack(field, raw: torch.Tensor) -> torch.Tensor:
     return out[: n.value]
 
 
+# ---- commitments: scl::util::Sha256, scl::util::MerkleTree<Sha256, FF> -------------------------------------------------------
+def _digests(*shape, device="cuda") -> torch.Tensor:
+    return torch.empty(*shape, 32, dtype=torch.uint8, device=device)
+
+
+def _index(idx, device):
+    """None, or a device tensor of 64-bit indices"""
+    if idx is None:
+        return None
+    t = torch.as_tensor(idx, dtype=torch.int64, device=device)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def sha256(msgs: torch.Tensor, msg_len: int | None = None) -> torch.Tensor:
+    """uint8 [count][stride] device buffer -> [count][32] digests of the first msg_len (default: stride) bytes of each row"""
+    if msgs.dtype != torch.uint8 or msgs.dim() != 2:
+        raise SclError(ERR_BAD_ARG, "sha256: a uint8 [count][stride] tensor is expected")
+    count, stride = msgs.shape
+    msg_len = stride if msg_len is None else msg_len
+    if msg_len > stride:
+        raise SclError(ERR_SIZE_MISMATCH, "sha256: msg_len exceeds the row length")
+    out = _digests(count, device=msgs.device)
+    _chk(lib.scl_hip_sha256(_dev(out), _dev(msgs) if msgs.numel() else None, C.c_size_t(msg_len), C.c_size_t(stride),
+                            C.c_size_t(count), _stream()))
+    return out
+
+
+def merkle_depth(L: int) -> int:
+    return lib.scl_hip_merkle_depth(C.c_size_t(L))
+
+
+def merkle_level_size(L: int, level: int) -> int:
+    return lib.scl_hip_merkle_level_size(C.c_size_t(L), C.c_size_t(level))
+
+
+def merkle_tree_bytes(L: int, T: int = 1) -> int:
+    return lib.scl_hip_merkle_tree_bytes(C.c_size_t(L), C.c_size_t(T))
+
+
+def merkle_leaves(field, a: torch.Tensor, out=None) -> torch.Tensor:
+    """elements [L][limbs] (one tree) or a share matrix [n][N][limbs] (N trees of n leaves; rows may sit a pitch apart)
+    -> leaf digests [L][32] / [n][N][32], the leaf level of merkle_build's layout"""
+    if a.dim() == 2:
+        a = a.unsqueeze(0)
+        shape = (a.shape[1],)
+    else:
+        shape = (a.shape[0], a.shape[1])
+    ptr, stride = _dev_rows(a)
+    rows, cols = a.shape[0], a.shape[1]
+    if out is None:
+        out = _digests(*shape, device=a.device)
+    elif out.dtype != torch.uint8 or out.numel() != rows * cols * 32:
+        raise SclError(ERR_SIZE_MISMATCH, "merkle_leaves: out must hold rows * cols digests")
+    _chk(lib.scl_hip_merkle_leaves(field, _dev(out), ptr, C.c_size_t(stride), C.c_size_t(rows), C.c_size_t(cols), _stream()))
+    return out
+
+
+def _leaf_shape(leaf_digests: torch.Tensor):
+    """(L, T) of leaf digests [L][32] or [L][T][32]"""
+    if leaf_digests.dtype != torch.uint8 or leaf_digests.shape[-1] != 32 or leaf_digests.dim() not in (2, 3):
+        raise SclError(ERR_BAD_ARG, "leaf digests: uint8 [L][32] or [L][T][32] expected")
+    return leaf_digests.shape[0], (leaf_digests.shape[1] if leaf_digests.dim() == 3 else 1)
+
+
+def merkle_build(leaf_digests: torch.Tensor) -> torch.Tensor:
+    """all levels of T trees of L leaves as one uint8 buffer (scl_hip.h: leaf-major, tree-minor, roots last)"""
+    L, T = _leaf_shape(leaf_digests)
+    tree = torch.empty(merkle_tree_bytes(L, T), dtype=torch.uint8, device=leaf_digests.device)
+    _chk(lib.scl_hip_merkle_build(_dev(tree), _dev(leaf_digests), C.c_size_t(L), C.c_size_t(T), _stream()))
+    return tree
+
+
+def merkle_root(leaf_digests: torch.Tensor) -> torch.Tensor:
+    """[T][32] roots, no levels kept"""
+    L, T = _leaf_shape(leaf_digests)
+    roots = _digests(T, device=leaf_digests.device)
+    _chk(lib.scl_hip_merkle_root(_dev(roots), _dev(leaf_digests), C.c_size_t(L), C.c_size_t(T), _stream()))
+    return roots
+
+
+def merkle_paths(tree: torch.Tensor, L: int, T: int = 1, leaf_index=None, tree_index=None, first_leaf: int = 0,
+                 k: int | None = None) -> torch.Tensor:
+    """[depth][k][32] siblings.  Index arrays (device int64) or the regular pattern tree = q mod T, leaf = first_leaf + q / T"""
+    li, ti = _index(leaf_index, tree.device), _index(tree_index, tree.device)
+    if k is None:
+        k = li.numel() if li is not None else ti.numel() if ti is not None else T
+    for t in (li, ti):
+        if t is not None and t.numel() != k:
+            raise SclError(ERR_SIZE_MISMATCH, "merkle_paths: an index array does not hold k entries")
+    if tree.numel() != merkle_tree_bytes(L, T):
+        raise SclError(ERR_SIZE_MISMATCH, "merkle_paths: the tree buffer does not have the size of (L, T)")
+    path = _digests(merkle_depth(L), k, device=tree.device)
+    _chk(lib.scl_hip_merkle_paths(_dev(path), _dev(tree), C.c_size_t(L), C.c_size_t(T), _dev(li) if li is not None else None,
+                                  _dev(ti) if ti is not None else None, C.c_size_t(first_leaf), C.c_size_t(k), _stream()))
+    return path
+
+
+def merkle_verify(leaf_digests: torch.Tensor, path: torch.Tensor, roots: torch.Tensor, leaf_index=None, leaf: int = 0,
+                  root_index=None) -> torch.Tensor:
+    """uint8 [k]: 1 where leaf digest q with path[:, q] and its leaf index hashes up to its root"""
+    depth, k = path.shape[0], path.shape[1]
+    li, ri = _index(leaf_index, path.device), _index(root_index, path.device)
+    if leaf_digests.numel() != k * 32 or any(t is not None and t.numel() != k for t in (li, ri)):
+        raise SclError(ERR_SIZE_MISMATCH, "merkle_verify: k leaf digests / indices expected")
+    ok = torch.empty(k, dtype=torch.uint8, device=path.device)
+    _chk(lib.scl_hip_merkle_verify(_dev(ok), _dev(leaf_digests), _dev(li) if li is not None else None, C.c_size_t(leaf),
+                                   _dev(path), C.c_size_t(depth), _dev(roots), _dev(ri) if ri is not None else None,
+                                   C.c_size_t(roots.numel() // 32), C.c_size_t(k), _stream()))
+    return ok
+
+
 def stream_copy(dst: torch.Tensor, src: torch.Tensor):
     _chk(lib.scl_hip_stream_copy(_dev(dst), _dev(src), C.c_size_t(src.numel() * src.element_size()), _stream()))
 
