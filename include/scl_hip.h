@@ -378,6 +378,56 @@ int scl_hip_merkle_verify(unsigned char* ok_dev, const unsigned char* leaf_diges
                           size_t leaf, const unsigned char* path_dev, size_t depth, const unsigned char* roots_dev,
                           const uint64_t* root_index_dev, size_t num_roots, size_t k, void* stream);
 
+/* ---- verifiable sharing: math::EC<Secp256k1> over vectors and Feldman VSS -----------------------------------------
+ * A point is 12 uint64_t: X, Y, Z of the homogeneous projective point, four limbs each in Montgomery form over
+ * SCL_SECP256K1_FIELD -- the reference's in-memory point (secp256k1_curve.cc:30-39); infinity is (0, 1, 0).  Point arrays are
+ * [count][12] and 16-byte aligned, scalars are SCL_SECP256K1_SCALAR elements (Montgomery limbs, 16-byte aligned).  Two points
+ * that are equal need not have equal limbs: compare with scl_hip_ec_equal or through scl_hip_ec_wire_pack.  Every call below
+ * that takes a stream is asynchronous on it, launches kernels and nothing else (capturable into a hipGraph), allocates nothing
+ * and returns SCL_OK at once for n == 0.  Errors: a NULL operand or a buffer that is not 16-byte aligned is SCL_ERR_BAD_ARG, a
+ * stride smaller than the row it strides over is SCL_ERR_SIZE_MISMATCH; scl_hip_last_error() has the text.
+ * Not built: compressed images, scalars that are math::Number, any other curve. */
+#define SCL_EC_OP_DBL 6 /* scl_hip_ec_ew only: dst = 2 a (EC::doublePoint, ec.h / secp256k1_curve.cc:232-274) */
+#define SCL_EC_POINT_LIMBS 12
+#define SCL_EC_WIRE_BYTES 65
+/* The generator (secp256k1_curve.cc:105-117) as a point; host only. */
+int scl_hip_ec_generator(uint64_t point_host[12]);
+/* Vector<EC> element-wise (vector.h add / subtract over EC: secp256k1_curve.cc:119-230, 276-290): op = SCL_OP_ADD, SCL_OP_SUB,
+ * SCL_OP_NEG (b_dev ignored) or SCL_EC_OP_DBL (b_dev ignored).  dst_dev may be a_dev or b_dev. */
+int scl_hip_ec_ew(int op, uint64_t* dst_dev, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, void* stream);
+/* EC::operator== per pair (secp256k1_curve.cc:77-84, cross-multiplication): eq_dev[i] = 1 or 0. */
+int scl_hip_ec_equal(unsigned char* eq_dev, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, void* stream);
+/* The window table of a base point B for scl_hip_ec_mul_base: 64 windows of 4 bits, each the affine multiples 1..15 of
+ * 16^w * B.  The caller owns the buffer of scl_hip_ec_base_table_bytes() bytes (device memory, 16-byte aligned); it is written
+ * once by this call and only read afterwards.  base_host is read before the call returns.  B = infinity: SCL_ERR_BAD_ARG. */
+size_t scl_hip_ec_base_table_bytes(void);
+int scl_hip_ec_base_table(void* table_dev, const uint64_t base_host[12], void* stream);
+/* dst_dev[i] = scalars_dev[i] * B (EC::operator*(FF<Scalar>), secp256k1_curve.cc:309-326) from B's table. */
+int scl_hip_ec_mul_base(uint64_t* dst_dev, const void* table_dev, const uint64_t* scalars_dev, size_t n, void* stream);
+/* dst_dev[i] = sum over k < m of scalars_dev[k] * points_dev[k * row_stride + i], i < n: m rows of n points and ONE scalar per
+ * row, read from device memory -- the sum of feldmanVerify (feldman.h:150-156).  m >= 1; dst_dev must not overlap points_dev. */
+int scl_hip_ec_lincomb(uint64_t* dst_dev, const uint64_t* points_dev, size_t row_stride, size_t m,
+                       const uint64_t* scalars_dev, size_t n, void* stream);
+/* Serializer<EC>::write / read (ec.h:315-339; secp256k1_curve.cc:357-431), always uncompressed: image i is the 65 bytes at
+ * i * 65 -- 0x04, x, y (affine, big-endian, out of Montgomery form), or 0x06 and 64 zero bytes for infinity.  Reading: the
+ * infinity flag (0x02) wins and the rest is ignored; a full point is not checked to lie on the curve; status_dev[i] = 0, or 1
+ * for an image with neither flag (a compressed point: not supported, the point written is infinity). */
+int scl_hip_ec_wire_pack(unsigned char* dst_dev, const uint64_t* points_dev, size_t n, void* stream);
+int scl_hip_ec_wire_unpack(uint64_t* points_dev, unsigned char* status_dev, const unsigned char* src_dev, size_t n,
+                           void* stream);
+/* The commitments of feldmanSecretShare (feldman.h:107-127) for N secrets: commit_dev[k * commit_stride + s] = f_s(k) * G,
+ * k = 0..t -- row 0 from secrets_dev[s], row k from share row k - 1 (shares_dev[(k - 1) * share_stride + s], the SoA share
+ * matrix of scl_hip_shamir_share*).  gtable_dev is the table of the generator. */
+int scl_hip_feldman_commit(uint64_t* commit_dev, size_t commit_stride, const void* gtable_dev, const uint64_t* secrets_dev,
+                           const uint64_t* shares_dev, size_t share_stride, size_t t, size_t N, void* stream);
+/* feldmanVerify (feldman.h:140-163) for N secrets at one index: ok_dev[s] = 1 iff sum_k lambda_k * commit[k][s] ==
+ * share_dev[s] * G.  lambda_dev: the t + 1 scalars of scl_hip_lagrange_basis(SCL_SECP256K1_SCALAR) over the nodes 0..t at
+ * the index, copied to the device by the caller (party p, 0-based, verifies at index p + 1; index 0 verifies the secret).
+ * scratch_points_dev: 2 N points owned by the caller. */
+int scl_hip_feldman_verify(unsigned char* ok_dev, const uint64_t* share_dev, const uint64_t* commit_dev, size_t commit_stride,
+                           size_t t, const uint64_t* lambda_dev, const void* gtable_dev, uint64_t* scratch_points_dev,
+                           size_t N, void* stream);
+
 /* ---- the open step: every party sends its shares to every party, then reconstructs ----------------------------
  * Replaces Network::send to each party + Network::recv from each party (include/scl/net/network.h:148-152,178-185; the
  * pattern of test/scl/protocol/beaver.h:43-55) followed by shamirRecoverP per secret (shamir.h:81-104), for a whole

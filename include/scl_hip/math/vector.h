@@ -10,6 +10,7 @@
 #ifndef SCL_HIP_MATH_VECTOR_H
 #define SCL_HIP_MATH_VECTOR_H
 
+#include <concepts>
 #include <cstdint>
 #include <initializer_list>
 #include <iterator>
@@ -130,10 +131,19 @@ class Vector final {
 
   Vector add(const Vector& o) const { return binary(SCL_OP_ADD, o); }
   Vector subtract(const Vector& o) const { return binary(SCL_OP_SUB, o); }
-  Vector multiplyEntryWise(const Vector& o) const { return binary(SCL_OP_MUL, o); }
+  /// (an element type without a product -- a group element, math::EC -- does not have this member: a compile error)
+  Vector multiplyEntryWise(const Vector& o) const
+    requires requires(const ELEMENT& a) { { a * a } -> std::convertible_to<ELEMENT>; }
+  {
+    return binary(SCL_OP_MUL, o);
+  }
   Vector& addInPlace(const Vector& o) { return *this = add(o); }
   Vector& subtractInPlace(const Vector& o) { return *this = subtract(o); }
-  Vector& multiplyEntryWiseInPlace(const Vector& o) { return *this = multiplyEntryWise(o); }
+  Vector& multiplyEntryWiseInPlace(const Vector& o)
+    requires requires(const ELEMENT& a) { { a * a } -> std::convertible_to<ELEMENT>; }
+  {
+    return *this = multiplyEntryWise(o);
+  }
 
   ELEMENT dot(const Vector& o) const {
     ensureCompatible(o);
@@ -246,9 +256,12 @@ class Vector final {
     if (hip::onHost<ELEMENT>(size())) {
       std::vector<ELEMENT> r;
       r.reserve(size());
-      for (std::size_t i = 0; i < m_values.size(); ++i)
-        r.emplace_back(op == SCL_OP_ADD ? m_values[i] + o.m_values[i]
-                                        : op == SCL_OP_SUB ? m_values[i] - o.m_values[i] : m_values[i] * o.m_values[i]);
+      for (std::size_t i = 0; i < m_values.size(); ++i) {
+        if (op == SCL_OP_ADD) r.emplace_back(m_values[i] + o.m_values[i]);
+        else if (op == SCL_OP_SUB) r.emplace_back(m_values[i] - o.m_values[i]);
+        else if constexpr (requires(const ELEMENT& a) { { a * a } -> std::convertible_to<ELEMENT>; }) r.emplace_back(m_values[i] * o.m_values[i]);
+        else hip::detail::unreachable();  // never reached: multiplyEntryWise requires the product
+      }
       return Vector(std::move(r));
     }
     if constexpr (OnDevice<ELEMENT>) {

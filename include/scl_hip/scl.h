@@ -4,11 +4,14 @@
 
 #include "hip/device.h"
 #include "hip/elementwise.h"
+#include "hip/feldman.h"
 #include "hip/merkle.h"
 #include "hip/open.h"
 #include "math/fields/ff_ops.h"
 #include "math/ff.h"
 #include "math/array.h"
+#include "math/curves/secp256k1.h"
+#include "math/ec.h"
 #include "math/lagrange.h"
 #include "math/matrix.h"
 #include "math/poly.h"
@@ -16,6 +19,7 @@
 #include "math/z2k.h"
 #include "serialization/serializer.h"
 #include "ss/additive.h"
+#include "ss/feldman.h"
 #include "ss/shamir.h"
 #include "util/bitmap.h"
 #include "util/digest.h"

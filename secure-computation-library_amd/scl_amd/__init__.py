@@ -688,6 +688,155 @@ def merkle_verify(leaf_digests: torch.Tensor, path: torch.Tensor, roots: torch.T
     return ok
 
 
+# ---- verifiable sharing: scl::math::EC<Secp256k1> over vectors, scl::ss::feldman* ---------------------------------------
+EC_DBL = 6          # SCL_EC_OP_DBL, for ec_ew only
+EC_LIMBS = 12       # X, Y, Z: four Montgomery limbs each
+EC_WIRE_BYTES = 65  # 0x04 | x | y
+
+
+def _points(t: torch.Tensor, what: str):
+    if t.dtype != torch.int64 or t.dim() < 2 or t.shape[-1] != EC_LIMBS:
+        raise SclError(ERR_BAD_ARG, f"{what}: int64 [..][12] points expected")
+    return t
+
+
+def ec_empty(*shape, device="cuda") -> torch.Tensor:
+    return torch.empty(*shape, EC_LIMBS, dtype=torch.int64, device=device)
+
+
+def ec_generator() -> np.ndarray:
+    g = np.zeros(EC_LIMBS, dtype=np.uint64)
+    _chk(lib.scl_hip_ec_generator(_hp(g)))
+    return g
+
+
+def ec_ew(op, a, b=None, out=None):
+    """points [n][12]: ADD, SUB (a, b), NEG, EC_DBL (a); out may be a or b"""
+    _points(a, "ec_ew a")
+    if b is not None and _points(b, "ec_ew b").shape != a.shape:
+        raise SclError(ERR_SIZE_MISMATCH, "")
+    if out is None:
+        out = torch.empty_like(a)
+    else:
+        _want(out, a.shape, "ec_ew out", a)
+    _chk(lib.scl_hip_ec_ew(op, _dev(out), _dev(a), _dev(b) if b is not None else None, C.c_size_t(a.numel() // EC_LIMBS),
+                           _stream()))
+    return out
+
+
+def ec_equal(a, b) -> torch.Tensor:
+    """uint8 [n]: 1 where a[i] == b[i] as points"""
+    if _points(a, "ec_equal a").shape != _points(b, "ec_equal b").shape:
+        raise SclError(ERR_SIZE_MISMATCH, "")
+    n = a.numel() // EC_LIMBS
+    eq = torch.empty(n, dtype=torch.uint8, device=a.device)
+    _chk(lib.scl_hip_ec_equal(_dev(eq), _dev(a), _dev(b), C.c_size_t(n), _stream()))
+    return eq
+
+
+def ec_base_table(base=None, device="cuda") -> torch.Tensor:
+    """the window table of a base point (host limbs [12]; default: the generator), owned by the caller"""
+    base = ec_generator() if base is None else _host(base).reshape(EC_LIMBS)
+    table = torch.empty(lib.scl_hip_ec_base_table_bytes(), dtype=torch.uint8, device=device)
+    _chk(lib.scl_hip_ec_base_table(_dev(table), _hp(base), _stream()))
+    return table
+
+
+def ec_mul_base(table, scalars, out=None):
+    """SECP256K1_SCALAR elements [n][4] -> points [n][12], scalars[i] * B for the table's base B"""
+    n = scalars.shape[0]
+    _want(scalars, (n, 4), "ec_mul_base scalars")
+    if out is None:
+        out = ec_empty(n, device=scalars.device)
+    else:
+        _want(out, (n, EC_LIMBS), "ec_mul_base out", scalars)
+    _chk(lib.scl_hip_ec_mul_base(_dev(out), _dev(table), _dev(scalars), C.c_size_t(n), _stream()))
+    return out
+
+
+def ec_lincomb(points, scalars, out=None):
+    """points [m][N][12] (rows may sit a pitch apart), scalars [m][4] on the device -> [N][12]: sum_k scalars[k] * points[k]"""
+    _points(points, "ec_lincomb points")
+    ptr, stride = _dev_rows(points)
+    m, N = points.shape[0], points.shape[1]
+    _want(scalars, (m, 4), "ec_lincomb scalars", points)
+    if out is None:
+        out = ec_empty(N, device=points.device)
+    else:
+        _want(out, (N, EC_LIMBS), "ec_lincomb out", points)
+    _chk(lib.scl_hip_ec_lincomb(_dev(out), ptr, C.c_size_t(stride), C.c_size_t(m), _dev(scalars), C.c_size_t(N), _stream()))
+    return out
+
+
+def ec_wire_pack(points) -> torch.Tensor:
+    """points [n][12] -> uint8 [n][65] Serializer<EC> images"""
+    n = _points(points, "ec_wire_pack").numel() // EC_LIMBS
+    out = torch.empty(n, EC_WIRE_BYTES, dtype=torch.uint8, device=points.device)
+    _chk(lib.scl_hip_ec_wire_pack(_dev(out), _dev(points), C.c_size_t(n), _stream()))
+    return out
+
+
+def ec_wire_unpack(raw):
+    """uint8 [n][65] -> (points [n][12], status uint8 [n]: non-zero for an image that is not uncompressed)"""
+    if raw.dtype != torch.uint8 or raw.dim() != 2 or raw.shape[1] != EC_WIRE_BYTES:
+        raise SclError(ERR_BAD_ARG, "ec_wire_unpack: a uint8 [n][65] tensor is expected")
+    n = raw.shape[0]
+    out = ec_empty(n, device=raw.device)
+    status = torch.empty(n, dtype=torch.uint8, device=raw.device)
+    _chk(lib.scl_hip_ec_wire_unpack(_dev(out), _dev(status), _dev(raw), C.c_size_t(n), _stream()))
+    return out, status
+
+
+def feldman_commit(gtable, secrets, shares, t: int, out=None):
+    """secrets [N][4], shares [n][N][4] (the SoA share matrix, n >= t) -> commitments [t + 1][N][12]"""
+    N = secrets.shape[0]
+    _want(secrets, (N, 4), "feldman_commit secrets")
+    if shares.dim() != 3 or shares.shape[0] < t or shares.shape[1] != N or shares.shape[2] != 4 or shares.dtype != torch.int64:
+        raise SclError(ERR_SIZE_MISMATCH, "feldman_commit: shares [n >= t][N][4] expected")
+    ptr, stride = _dev_rows(shares)
+    if out is None:
+        out = ec_empty(t + 1, N, device=secrets.device)
+    else:
+        _want(out, (t + 1, N, EC_LIMBS), "feldman_commit out", secrets)
+    _chk(lib.scl_hip_feldman_commit(_dev(out), C.c_size_t(N), _dev(gtable), _dev(secrets), ptr, C.c_size_t(stride),
+                                    C.c_size_t(t), C.c_size_t(N), _stream()))
+    return out
+
+
+def feldman_lambda(t: int, index: int, device="cuda") -> torch.Tensor:
+    """the Lagrange basis over the nodes 0..t at `index` (feldman.h:139-140), on the device"""
+    nodes = np.stack([_mont_small(k) for k in range(t + 1)])
+    return to_device(lagrange_basis(SECP256K1_SCALAR, t + 1, nodes, _mont_small(index)), device)
+
+
+def _mont_small(v: int) -> np.ndarray:
+    """v as a SECP256K1_SCALAR element (Montgomery limbs)"""
+    q = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
+    m = (v % q) * (1 << 256) % q
+    return np.array([(m >> (64 * i)) & (2 ** 64 - 1) for i in range(4)], dtype=np.uint64)
+
+
+def feldman_verify(gtable, share, commitments, lam, scratch=None, out=None):
+    """share [N][4], commitments [t + 1][N][12], lam = feldman_lambda(t, index) -> uint8 [N] verdicts"""
+    N = share.shape[0]
+    _want(share, (N, 4), "feldman_verify share")
+    _points(commitments, "feldman_verify commitments")
+    ptr, stride = _dev_rows(commitments)
+    t = commitments.shape[0] - 1
+    _want(lam, (t + 1, 4), "feldman_verify lambda", share)
+    if commitments.shape[1] != N:
+        raise SclError(ERR_SIZE_MISMATCH, "feldman_verify: commitments [t + 1][N][12] expected")
+    if scratch is None:
+        scratch = ec_empty(2 * N, device=share.device)
+    else:
+        _want(scratch, (2 * N, EC_LIMBS), "feldman_verify scratch", share)
+    if out is None:
+        out = torch.empty(N, dtype=torch.uint8, device=share.device)
+    _chk(lib.scl_hip_feldman_verify(_dev(out), _dev(share), ptr, C.c_size_t(stride), C.c_size_t(t), _dev(lam), _dev(gtable),
+                                    _dev(scratch), C.c_size_t(N), _stream()))
+    return out
+
+
 def stream_copy(dst: torch.Tensor, src: torch.Tensor):
     _chk(lib.scl_hip_stream_copy(_dev(dst), _dev(src), C.c_size_t(src.numel() * src.element_size()), _stream()))
 
