@@ -428,6 +428,43 @@ int scl_hip_feldman_verify(unsigned char* ok_dev, const uint64_t* share_dev, con
                            size_t t, const uint64_t* lambda_dev, const void* gtable_dev, uint64_t* scratch_points_dev,
                            size_t N, void* stream);
 
+/* ---- ECDSA over secp256k1: scl::util::ECDSA (include/scl/util/sign.h) over batches ---------------------------------------------
+ * A signature is 8 limbs, r then s, each a SCL_SECP256K1_SCALAR element; arrays are [n][8].  The 64-byte image of
+ * Signature<ECDSA>::write (sign.h:59-71) is the images of r and s one after the other, so the byte image of n signatures is the
+ * byte image of 2 n scalars: scl_hip_from_bytes over SCL_SECP256K1_SCALAR with 2 n elements reads it, scl_hip_wire_pack writes
+ * it behind its 4-byte count.
+ * Digests are [n][32] bytes, what a row of scl_hip_sha256's output is: digestToElement (sign.h:169-177) for a 32-byte digest,
+ * read big-endian and reduced mod the group order.  (A shorter digest goes to the FRONT of a zeroed 32-byte row, a longer one
+ * gives its first 32 bytes: the caller's layout, not a kernel's.)  Keys: secret keys are scalars, public keys points; each
+ * call takes ONE key for all signatures (stride 0) or one per signature (stride 1).  Nothing here allocates, copies or
+ * synchronises: the calls capture into a hipGraph.
+ *
+ * dst_dev[i] = scalars_dev[i] * points_dev[i] (EC::operator*(FF<Scalar>) over a vector, secp256k1_curve.cc:309-326): a point
+ * and a scalar per lane, 4-bit windows over a table of the lane's own in scratch_dev -- scl_hip_ec_mul_scratch_bytes(n) bytes
+ * of device memory, 16-byte aligned, owned by the caller, contents meaningless between calls.  dst_dev may be points_dev. */
+size_t scl_hip_ec_mul_scratch_bytes(size_t n);
+int scl_hip_ec_mul(uint64_t* dst_dev, const uint64_t* points_dev, const uint64_t* scalars_dev, void* scratch_dev, size_t n,
+                   void* stream);
+/* ECDSA::conversionFunc (sign.h:157-162) per point: the affine x as an integer, mod the group order; infinity gives 0. */
+int scl_hip_ecdsa_conversion(uint64_t* scalars_dev, const uint64_t* points_dev, size_t n, void* stream);
+/* ECDSA::Sign (sign.h:116-126) with the nonces supplied: sig_dev[i] = (r, s), r = conversionFunc(nonces_dev[i] * G),
+ * s = nonces_dev[i]^-1 * (h_i + sk * r).  The library draws no nonce: the caller fills nonces_dev (the reference draws
+ * SecretKey::random(prg) per signature).  A zero nonce, where the reference's inverse throws (ff_ops_gmp.h:250-260), writes
+ * (0, 0) and sets *status_dev (one 32-bit device word, never cleared by the call, may be NULL) to 1; r == 0 or s == 0 for any
+ * other reason is not checked, as in the reference.  gtable_dev is the table of the generator. */
+int scl_hip_ecdsa_sign(uint64_t* sig_dev, const void* gtable_dev, const uint64_t* sk_dev, size_t sk_stride,
+                       const uint64_t* nonces_dev, const unsigned char* digests_dev, unsigned* status_dev, size_t n, void* stream);
+/* ECDSA::verify (sign.h:135-146) per signature: verdict_dev[i] = 1 accepted, 0 rejected, 2 where s == 0 (the reference's
+ * s.inverse() throws there).  Every lane inverts its own s, so a zero has no effect on its neighbours.  scratch_dev as for
+ * scl_hip_ec_mul.  Public keys are not checked to lie on the curve. */
+int scl_hip_ecdsa_verify(unsigned char* verdict_dev, const uint64_t* sig_dev, const unsigned char* digests_dev,
+                         const uint64_t* pk_dev, size_t pk_stride, const void* gtable_dev, void* scratch_dev, size_t n,
+                         void* stream);
+/* The same verdicts when every signature is ONE signer's: qtable_dev is the window table of the public key
+ * (scl_hip_ec_base_table), and no scratch is needed. */
+int scl_hip_ecdsa_verify_base(unsigned char* verdict_dev, const uint64_t* sig_dev, const unsigned char* digests_dev,
+                              const void* qtable_dev, const void* gtable_dev, size_t n, void* stream);
+
 /* ---- the open step: every party sends its shares to every party, then reconstructs ----------------------------
  * Replaces Network::send to each party + Network::recv from each party (include/scl/net/network.h:148-152,178-185; the
  * pattern of test/scl/protocol/beaver.h:43-55) followed by shamirRecoverP per secret (shamir.h:81-104), for a whole

@@ -13,7 +13,8 @@
 // not a Montgomery product): add 12 M + 2 c, mixed add (Z2 = 1) 11 M + 2 c, dbl 8 M + 1 c (squares counted as M:
 // Mont256::sqr is mul), equality 4 M, to affine 1 inversion (270 M: 255 squares, 15 products) + 2 M.
 //
-// This header is new with the Feldman entry points and is deliberately not part of field.hpp.
+// This header is new with the Feldman entry points and is deliberately not part of field.hpp.  Its last section is what ECDSA
+// adds: the scalar field's inversion, the conversion function and the per-lane window ladder (csrc/ecdsa_unit.hip).
 #pragma once
 #include "field.hpp"
 
@@ -30,7 +31,7 @@ struct Point {
 struct Affine {
   Fe x, y;
 };
-enum { POINT_LIMBS = 12, AFFINE_LIMBS = 8, WIRE_BYTES = 65, WINDOWS = 64, WINDOW_ENTRIES = 15 };
+enum { POINT_LIMBS = 12, AFFINE_LIMBS = 8, WIRE_BYTES = 65, WINDOWS = 64, WINDOW_ENTRIES = 15, MUL_TABLE_ENTRIES = 16 };
 // ec::toBytes / fromBytes flag bits (secp256k1_curve.cc:328-339)
 enum { FLAG_FULL_POINT = 0x04, FLAG_INFINITY = 0x02 };
 
@@ -212,6 +213,123 @@ SCL_HD Point pt_mul(const Point& p, const Fe& scalar_mont) {
     if ((k.w[i >> 6] >> (i & 63)) & 1) r = pt_add(r, p);
   }
   return r;
+}
+
+// ---- ECDSA (util::ECDSA, include/scl/util/sign.h:87-178): what signing and verification need beyond the group law -----------
+SCL_HD Fe rmul(const Fe& a, const Fe& b) { return FR::mul(FR::Ctx{}, a, b); }
+SCL_HD Fe rsqn(Fe a, int n) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 0; i < n; ++i) a = rmul(a, a);
+  return a;
+}
+// a^(q - 2) in the scalar field; rinv(0) = 0.  q - 2 is 127 ones, a zero, and 128 bits without structure (69 of them set): the
+// run is built by doubling its length as in finv (x_k = a^(2^k - 1); 126 squares, 12 products), the rest is a rolled
+// square-and-multiply over the constant -- the bit is the same in every lane, so the branch is uniform.  255 squares and
+// 81 products; no table, so no indexed array in registers.
+SCL_HD Fe rinv(const Fe& a) {
+  Fe x = a;  // x_1
+  int k = 1;
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int step = 0; step < 6; ++step) {  // x_k -> x_2k -> x_(2k + 1): 1, 3, 7, 15, 31, 63, 127
+    x = rmul(rsqn(x, k), x);
+    x = rmul(rsqn(x, 1), a);
+    k = 2 * k + 1;
+  }
+  x = rsqn(x, 1);  // the zero that ends the run
+  const u64 lo = FR::P(0) - 2, hi = FR::P(1);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int i = 127; i >= 0; --i) {
+    x = rsqn(x, 1);
+    if (((i >= 64 ? hi : lo) >> (i & 63)) & 1) x = rmul(x, a);
+  }
+  return x;
+}
+
+// the integer 32 big-endian bytes spell (not reduced, not in Montgomery form)
+SCL_HD Fe u256_read_be(const unsigned char* src) {
+  Fe v;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    u64 w = 0;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) w = (w << 8) | src[8 * i + b];
+    v.w[3 - i] = w;
+  }
+  return v;
+}
+// FF<Secp256k1Scalar>::read (montyFromBytes -> montyIn, ff_ops_gmp.h:280-290): 32 big-endian bytes, any value below 2^256,
+// reduced mod q by the Montgomery product with R^2 (valid for a first operand below 2^256)
+SCL_HD Fe scalar_from_be32(const unsigned char* src) { return FR::to_mont(FR::Ctx{}, u256_read_be(src)); }
+
+// ECDSA::conversionFunc (sign.h:157-162): the affine x written big-endian and read back mod q.  x < p < 2^256 goes into the
+// scalar field's Montgomery form as any 256-bit integer does.  Of infinity: finv(0) = 0, so x = 0 and the result is 0.
+SCL_HD Fe ecdsa_conversion(const Point& p) {
+  const Fe x = FQ::from_mont(FQ::Ctx{}, fmul(p.X, finv(p.Z)));
+  return FR::to_mont(FR::Ctx{}, x);
+}
+
+// "R is not infinity and x(R) mod q == r" for a plain integer r < q, without the inversion: x(R) < p < 2 q, so x mod q == r
+// iff x == r or x == r + q, the second only when r + q < p; and x == v iff X == v Z.  q in the coordinate field's
+// Montgomery form is a constant, so v = r + q costs an addition: three products (r into Montgomery form, r Z, (r + q) Z).
+SCL_HD bool pt_x_is(const Point& p, const Fe& r_plain) {
+  const Fe q_mont = FQ::make(0xE21120489F1D95E1ull, 0x24A1AC9EB3FDE294ull, 0xFFFFFFFEBAAED80Dull, 0xFFFFFFFFFFFFFFFFull);  // q 2^256 mod p
+  const Fe r = FQ::to_mont(FQ::Ctx{}, r_plain);
+  Fe sum;
+  const u64 carry = FQ::add_n(sum, r_plain, FR::prime());
+  const bool second = !carry && !FQ::geq_p(sum);  // r + q < p
+  const bool e0 = FQ::eq(p.X, fmul(r, p.Z));
+  const bool e1 = FQ::eq(p.X, fmul(fadd(r, q_mont), p.Z));
+  return (!pt_is_infinity(p)) & (e0 | (second & e1));
+}
+
+// acc + k * B from B's window table (k_ec_base_table's layout: entry (w, d - 1) is the affine d 16^w B): 64 mixed additions.
+// A zero digit has no affine operand; the lane adds entry 1 of the window like the others and keeps its old sum.
+SCL_HD Point pt_add_mul_table(Point acc, const u64* table, const Fe& k_plain) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int w = 0; w < WINDOWS; ++w) {
+    const unsigned d = scalar_digit(k_plain, w);
+    const u64* ent = table + ((size_t)w * WINDOW_ENTRIES + (d ? d - 1 : 0)) * AFFINE_LIMBS;
+    const Affine q{FQ::ld(ent), FQ::ld(ent + 4)};
+    acc = pt_select(d != 0, pt_add_affine(acc, q), acc);
+  }
+  return acc;
+}
+
+// k * P for a point and a scalar of the lane's own, in 4-bit windows.  The lane writes its table of d P, d = 0..15 (entry 0 is
+// infinity: the formulas are complete, so a zero digit needs neither a branch nor a select), to memory it was given -- entry d
+// at table + d * pitch limbs -- by 7 doublings and 7 additions, then runs 64 windows of 4 doublings and one table addition
+// from the top digit down.  The digit only picks an address.
+SCL_HD Point pt_mul_window(const Point& p, const Fe& k_plain, u64* table, size_t pitch) {
+  pt_store(table, pt_infinity());
+  pt_store(table + pitch, p);
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int j = 1; j < 8; ++j) {
+    const Point even = pt_dbl(pt_load(table + (size_t)j * pitch));
+    pt_store(table + (size_t)(2 * j) * pitch, even);
+    pt_store(table + (size_t)(2 * j + 1) * pitch, pt_add(even, p));
+  }
+  Point acc = pt_infinity();
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+  for (int w = WINDOWS - 1; w >= 0; --w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+    for (int i = 0; i < 4; ++i) acc = pt_dbl(acc);
+    acc = pt_add(acc, pt_load(table + (size_t)scalar_digit(k_plain, w) * pitch));
+  }
+  return acc;
 }
 
 }  // namespace secp

@@ -837,6 +837,107 @@ def feldman_verify(gtable, share, commitments, lam, scratch=None, out=None):
     return out
 
 
+# ---- signatures: scl::util::ECDSA over batches ----------------------------------------------------------------------------
+def ec_mul_scratch(n: int, device="cuda") -> torch.Tensor:
+    """the window-table scratch of ec_mul / ecdsa_verify for n items (contents meaningless between calls)"""
+    return torch.empty(lib.scl_hip_ec_mul_scratch_bytes(C.c_size_t(n)), dtype=torch.uint8, device=device)
+
+
+def _mul_scratch(scratch, n: int, like: torch.Tensor, what: str):
+    if scratch is None:
+        return ec_mul_scratch(n, device=like.device)
+    if scratch.dtype != torch.uint8 or scratch.numel() < lib.scl_hip_ec_mul_scratch_bytes(C.c_size_t(n)) or scratch.device != like.device:
+        raise SclError(ERR_SIZE_MISMATCH, f"{what}: scratch must be uint8, of ec_mul_scratch(n)'s size")
+    return scratch
+
+
+def ec_mul(points, scalars, scratch=None, out=None):
+    """points [n][12], SECP256K1_SCALAR elements [n][4] -> [n][12]: scalars[i] * points[i]; out may be points"""
+    n = scalars.shape[0]
+    _want(scalars, (n, 4), "ec_mul scalars")
+    _want(_points(points, "ec_mul points"), (n, EC_LIMBS), "ec_mul points", scalars)
+    if out is None:
+        out = ec_empty(n, device=scalars.device)
+    else:
+        _want(out, (n, EC_LIMBS), "ec_mul out", scalars)
+    scratch = _mul_scratch(scratch, n, scalars, "ec_mul")
+    _chk(lib.scl_hip_ec_mul(_dev(out), _dev(points), _dev(scalars), _dev(scratch), C.c_size_t(n), _stream()))
+    return out
+
+
+def ecdsa_conversion(points, out=None):
+    """points [n][12] -> SECP256K1_SCALAR elements [n][4]: the affine x mod the group order (ECDSA::conversionFunc)"""
+    n = _points(points, "ecdsa_conversion").numel() // EC_LIMBS
+    if out is None:
+        out = torch.empty(n, 4, dtype=torch.int64, device=points.device)
+    else:
+        _want(out, (n, 4), "ecdsa_conversion out", points)
+    _chk(lib.scl_hip_ecdsa_conversion(_dev(out), _dev(points), C.c_size_t(n), _stream()))
+    return out
+
+
+def _digest_rows(digests, n: int, what: str):
+    if digests.dtype != torch.uint8 or tuple(digests.shape) != (n, 32):
+        raise SclError(ERR_SIZE_MISMATCH, f"{what}: digests must be uint8 [n][32]")
+    return digests
+
+
+def ecdsa_sign(gtable, sk, nonces, digests, status=None, out=None):
+    """sk [1][4] (one key) or [n][4], nonces [n][4], digests uint8 [n][32] -> signatures [n][8] (r then s).  A zero nonce writes
+    (0, 0) and sets `status` (ew_status_buffer(), never cleared here) to 1."""
+    n = nonces.shape[0]
+    _want(nonces, (n, 4), "ecdsa_sign nonces")
+    if sk.shape[0] not in (1, n):
+        raise SclError(ERR_SIZE_MISMATCH, "ecdsa_sign: one secret key, or one per signature")
+    _want(sk, (sk.shape[0], 4), "ecdsa_sign sk", nonces)
+    _digest_rows(digests, n, "ecdsa_sign")
+    if status is not None and (status.dtype != torch.int32 or status.numel() != 1 or not status.is_cuda):
+        raise SclError(ERR_BAD_ARG, "status: one int32 element on the GPU")
+    if out is None:
+        out = torch.empty(n, 8, dtype=torch.int64, device=nonces.device)
+    else:
+        _want(out, (n, 8), "ecdsa_sign out", nonces)
+    _chk(lib.scl_hip_ecdsa_sign(_dev(out), _dev(gtable), _dev(sk), C.c_size_t(0 if sk.shape[0] == 1 else 1), _dev(nonces),
+                                _dev(digests), _dev(status) if status is not None else None, C.c_size_t(n), _stream()))
+    return out
+
+
+def _verdicts(out, n: int, like: torch.Tensor, what: str):
+    """the uint8 [n] verdict buffer of a verification: a new one, or the caller's after the checks _want makes for limbs"""
+    if out is None:
+        return torch.empty(n, dtype=torch.uint8, device=like.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (n,) or out.device != like.device:
+        raise SclError(ERR_SIZE_MISMATCH, f"{what}: out must be uint8 [n] on the signatures' device")
+    return out
+
+
+def ecdsa_verify(gtable, pk, sig, digests, scratch=None, out=None):
+    """pk [1][12] (one key) or [n][12], signatures [n][8], digests uint8 [n][32] -> uint8 [n]: 1 accepted, 0 rejected, 2 s == 0"""
+    n = sig.shape[0]
+    _want(sig, (n, 8), "ecdsa_verify signatures")
+    _points(pk, "ecdsa_verify pk")
+    if pk.dim() != 2 or pk.shape[0] not in (1, n):
+        raise SclError(ERR_SIZE_MISMATCH, "ecdsa_verify: one public key, or one per signature")
+    _digest_rows(digests, n, "ecdsa_verify")
+    scratch = _mul_scratch(scratch, n, sig, "ecdsa_verify")
+    out = _verdicts(out, n, sig, "ecdsa_verify")
+    _chk(lib.scl_hip_ecdsa_verify(_dev(out), _dev(sig), _dev(digests), _dev(pk), C.c_size_t(0 if pk.shape[0] == 1 else 1),
+                                  _dev(gtable), _dev(scratch), C.c_size_t(n), _stream()))
+    return out
+
+
+def ecdsa_verify_base(gtable, qtable, sig, digests, out=None):
+    """the verdicts of ecdsa_verify for ONE signer, from the window table of the signer's key (ec_base_table(pk))"""
+    n = sig.shape[0]
+    _want(sig, (n, 8), "ecdsa_verify_base signatures")
+    _digest_rows(digests, n, "ecdsa_verify_base")
+    if qtable.numel() * qtable.element_size() != lib.scl_hip_ec_base_table_bytes():
+        raise SclError(ERR_SIZE_MISMATCH, "ecdsa_verify_base: qtable is not a window table")
+    out = _verdicts(out, n, sig, "ecdsa_verify_base")
+    _chk(lib.scl_hip_ecdsa_verify_base(_dev(out), _dev(sig), _dev(digests), _dev(qtable), _dev(gtable), C.c_size_t(n), _stream()))
+    return out
+
+
 def stream_copy(dst: torch.Tensor, src: torch.Tensor):
     _chk(lib.scl_hip_stream_copy(_dev(dst), _dev(src), C.c_size_t(src.numel() * src.element_size()), _stream()))
 
