@@ -215,7 +215,8 @@ int scl_hip_shamir_share_prg(int field, uint64_t* shares_dev, size_t share_strid
  * (t+1)*W elements and component j of coefficient k is element k*W + j; arithmetic is component-wise, nodes 1..n.
  * secrets_dev: component j at secrets_dev + j * secret_stride elements; shares_dev: component j, party i at
  * shares_dev + (j * n + i) * share_stride elements.  Secret s starts at block counter0 + s * ceil((t+1)*W*byteSize/16).
- * The EC commitments of Feldman / Pedersen stay with the caller. */
+ * The EC commitments are calls of their own over this layout: scl_hip_feldman_commit for a width of one,
+ * scl_hip_pedersen_commit for the {secret, blinding} pairs of width = 2. */
 int scl_hip_shamir_share_prg_packed(int field, uint64_t* shares_dev, size_t share_stride, const uint64_t* secrets_dev,
                                     size_t secret_stride, size_t N, size_t t, size_t n, size_t width,
                                     const unsigned char* seed_host, size_t seed_len, uint64_t counter0, void* stream);
@@ -386,6 +387,8 @@ int scl_hip_merkle_verify(unsigned char* ok_dev, const unsigned char* leaf_diges
  * that takes a stream is asynchronous on it, launches kernels and nothing else (capturable into a hipGraph), allocates nothing
  * and returns SCL_OK at once for n == 0.  Errors: a NULL operand or a buffer that is not 16-byte aligned is SCL_ERR_BAD_ARG, a
  * stride smaller than the row it strides over is SCL_ERR_SIZE_MISMATCH; scl_hip_last_error() has the text.
+ * Pedersen VSS (the second block of entries below) takes a second base H as a window table of its own; H is any finite point
+ * (scl_hip_ec_base_table refuses infinity, and Pedersen inherits that).
  * Not built: compressed images, scalars that are math::Number, any other curve. */
 #define SCL_EC_OP_DBL 6 /* scl_hip_ec_ew only: dst = 2 a (EC::doublePoint, ec.h / secp256k1_curve.cc:232-274) */
 #define SCL_EC_POINT_LIMBS 12
@@ -427,6 +430,32 @@ int scl_hip_feldman_commit(uint64_t* commit_dev, size_t commit_stride, const voi
 int scl_hip_feldman_verify(unsigned char* ok_dev, const uint64_t* share_dev, const uint64_t* commit_dev, size_t commit_stride,
                            size_t t, const uint64_t* lambda_dev, const void* gtable_dev, uint64_t* scratch_points_dev,
                            size_t N, void* stream);
+
+/* dst_dev[i] = a_dev[i] * G + b_dev[i] * H from the window tables of G and H (the commitment of pedersen.h:143,145 and the
+ * right-hand side of pedersenVerify, pedersen.h:206): one accumulator, 128 mixed additions, no doubling. */
+int scl_hip_ec_mul_two_base(uint64_t* dst_dev, const void* gtable_dev, const void* htable_dev, const uint64_t* a_dev,
+                            const uint64_t* b_dev, size_t n, void* stream);
+/* The point side of ss::apply (pedersen.h:262-271): dst_dev[i * dst_stride + c] = sum over k < p of M_dev[i * p + k] *
+ * points_dev[k * row_stride + c], i < rows, c < cols -- a rows x p matrix of scalars (row-major, device memory) times a p x cols
+ * matrix of points.  The doubling chain of output row i starts at the highest bit set in row i of M, so a matrix of small
+ * entries (identity, Vandermonde) costs in proportion to its bit length; a row of zeros gives infinity.  p >= 1;
+ * dst_dev must not overlap points_dev (SCL_ERR_BAD_ARG). */
+int scl_hip_ec_matmul(uint64_t* dst_dev, size_t dst_stride, const uint64_t* M_dev, size_t rows, size_t p,
+                      const uint64_t* points_dev, size_t row_stride, size_t cols, void* stream);
+/* The commitments of pedersenSecretShare (pedersen.h:140-146) for N secrets over the packed layout of
+ * scl_hip_shamir_share_prg_packed with width = 2: component j of the secret at secrets_dev + j * secret_stride, component j of
+ * party i at shares_dev + (j * n + i) * share_stride (strides in elements).  commit_dev[0 * commit_stride + s] = secret_s * G +
+ * blinding_s * H, row k = 1..t from party k - 1.  n < t: SCL_ERR_SIZE_MISMATCH.  htable_dev is the table of H. */
+int scl_hip_pedersen_commit(uint64_t* commit_dev, size_t commit_stride, const void* gtable_dev, const void* htable_dev,
+                            const uint64_t* secrets_dev, size_t secret_stride, const uint64_t* shares_dev, size_t share_stride,
+                            size_t t, size_t n, size_t N, void* stream);
+/* pedersenVerify (pedersen.h:178-207) for N secrets at one index: ok_dev[s] = 1 iff sum_k lambda_k * commit[k][s] ==
+ * share_dev[s] * G + rand_dev[s] * H.  lambda_dev as for scl_hip_feldman_verify: the basis over the nodes 0..t at the index; the
+ * reference's shortcut for an index <= t (pedersen.h:181-183) is the unit-vector case of the same sum.  scratch_points_dev: 2 N
+ * points owned by the caller. */
+int scl_hip_pedersen_verify(unsigned char* ok_dev, const uint64_t* share_dev, const uint64_t* rand_dev, const uint64_t* commit_dev,
+                            size_t commit_stride, size_t t, const uint64_t* lambda_dev, const void* gtable_dev,
+                            const void* htable_dev, uint64_t* scratch_points_dev, size_t N, void* stream);
 
 /* ---- ECDSA over secp256k1: scl::util::ECDSA (include/scl/util/sign.h) over batches ---------------------------------------------
  * A signature is 8 limbs, r then s, each a SCL_SECP256K1_SCALAR element; arrays are [n][8].  The 64-byte image of

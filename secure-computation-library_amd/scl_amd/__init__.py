@@ -837,6 +837,83 @@ def feldman_verify(gtable, share, commitments, lam, scratch=None, out=None):
     return out
 
 
+# ---- scl::ss::pedersen*: a second base H (a window table of its own, ec_base_table(h)) beside the generator ----------------
+def ec_mul_two_base(gtable, htable, a, b, out=None):
+    """SECP256K1_SCALAR elements a, b [n][4] -> points [n][12], a[i] * G + b[i] * H for the tables' bases"""
+    n = a.shape[0]
+    _want(a, (n, 4), "ec_mul_two_base a")
+    _want(b, (n, 4), "ec_mul_two_base b", a)
+    if out is None:
+        out = ec_empty(n, device=a.device)
+    else:
+        _want(out, (n, EC_LIMBS), "ec_mul_two_base out", a)
+    _chk(lib.scl_hip_ec_mul_two_base(_dev(out), _dev(gtable), _dev(htable), _dev(a), _dev(b), C.c_size_t(n), _stream()))
+    return out
+
+
+def ec_matmul(matrix, points, out=None):
+    """matrix [rows][p][4] scalars on the device, points [p][cols][12] (rows may sit a pitch apart) -> [rows][cols][12]:
+    out[i][c] = sum_k matrix[i][k] * points[k][c], the commitment side of ss::apply"""
+    _points(points, "ec_matmul points")
+    if points.dim() != 3:
+        raise SclError(ERR_BAD_ARG, "ec_matmul: points [p][cols][12] expected")
+    ptr, stride = _dev_rows(points)
+    p, cols = points.shape[0], points.shape[1]
+    if matrix.dim() != 3 or matrix.shape[1] != p:
+        raise SclError(ERR_SIZE_MISMATCH, "ec_matmul: matrix [rows][p][4] expected")
+    rows = matrix.shape[0]
+    _want(matrix, (rows, p, 4), "ec_matmul matrix", points)
+    if out is None:
+        out = ec_empty(rows, cols, device=points.device)
+    else:
+        _want(out, (rows, cols, EC_LIMBS), "ec_matmul out", points)
+    _chk(lib.scl_hip_ec_matmul(_dev(out), C.c_size_t(cols), _dev(matrix), C.c_size_t(rows), C.c_size_t(p), ptr, C.c_size_t(stride),
+                               C.c_size_t(cols), _stream()))
+    return out
+
+
+def pedersen_commit(gtable, htable, secrets, shares, t: int, out=None):
+    """secrets [2][N][4] ({secret, blinding}), shares [2][n][N][4] (shamir_share_prg_packed's layout, n >= t) -> commitments
+    [t + 1][N][12]"""
+    if secrets.dim() != 3 or secrets.shape[0] != 2:
+        raise SclError(ERR_SIZE_MISMATCH, "pedersen_commit: secrets [2][N][4] expected")
+    N = secrets.shape[1]
+    _want(secrets, (2, N, 4), "pedersen_commit secrets")
+    if shares.dim() != 4 or shares.shape[0] != 2 or shares.shape[1] < t or shares.shape[2] != N:
+        raise SclError(ERR_SIZE_MISMATCH, "pedersen_commit: shares [2][n >= t][N][4] expected")
+    n = shares.shape[1]
+    _want(shares, (2, n, N, 4), "pedersen_commit shares", secrets)
+    if out is None:
+        out = ec_empty(t + 1, N, device=secrets.device)
+    else:
+        _want(out, (t + 1, N, EC_LIMBS), "pedersen_commit out", secrets)
+    _chk(lib.scl_hip_pedersen_commit(_dev(out), C.c_size_t(N), _dev(gtable), _dev(htable), _dev(secrets), C.c_size_t(N),
+                                     _dev(shares), C.c_size_t(N), C.c_size_t(t), C.c_size_t(n), C.c_size_t(N), _stream()))
+    return out
+
+
+def pedersen_verify(gtable, htable, share, rand, commitments, lam, scratch=None, out=None):
+    """share, rand [N][4], commitments [t + 1][N][12], lam = feldman_lambda(t, index) -> uint8 [N] verdicts"""
+    N = share.shape[0]
+    _want(share, (N, 4), "pedersen_verify share")
+    _want(rand, (N, 4), "pedersen_verify rand", share)
+    _points(commitments, "pedersen_verify commitments")
+    ptr, stride = _dev_rows(commitments)
+    t = commitments.shape[0] - 1
+    _want(lam, (t + 1, 4), "pedersen_verify lambda", share)
+    if commitments.shape[1] != N:
+        raise SclError(ERR_SIZE_MISMATCH, "pedersen_verify: commitments [t + 1][N][12] expected")
+    if scratch is None:
+        scratch = ec_empty(2 * N, device=share.device)
+    else:
+        _want(scratch, (2 * N, EC_LIMBS), "pedersen_verify scratch", share)
+    if out is None:
+        out = torch.empty(N, dtype=torch.uint8, device=share.device)
+    _chk(lib.scl_hip_pedersen_verify(_dev(out), _dev(share), _dev(rand), ptr, C.c_size_t(stride), C.c_size_t(t), _dev(lam),
+                                     _dev(gtable), _dev(htable), _dev(scratch), C.c_size_t(N), _stream()))
+    return out
+
+
 # ---- signatures: scl::util::ECDSA over batches ----------------------------------------------------------------------------
 def ec_mul_scratch(n: int, device="cuda") -> torch.Tensor:
     """the window-table scratch of ec_mul / ecdsa_verify for n items (contents meaningless between calls)"""
