@@ -44,6 +44,9 @@
  *    once built (device tables of Vandermonde rows, behind a mutex; a caller holds a reference to the table it uses
  *    until its kernel is enqueued, and past 16 entries the least recently used one is freed once nobody holds it).
  *    A thread that exits calls scl_hip_thread_cleanup() to release its device buffers.
+ *  - protocol arithmetic over these entry points (Beaver multiplication: the mask before the open step and the finish
+ *    after it) is a library of its own beside this one, libscl_hip_mpc.so with include/scl_hip_mpc.h; it adds no
+ *    prototype here and uses nothing but the prototypes below.
  */
 #ifndef SCL_HIP_H
 #define SCL_HIP_H

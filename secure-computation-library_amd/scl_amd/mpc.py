@@ -1,0 +1,140 @@
+"""scl_amd.mpc -- Python harness over libscl_hip_mpc.so, the protocol extension beside the engine (include/scl_hip_mpc.h).
+
+Beaver multiplication of shared vectors (the reference's BeaverMul, test/scl/protocol/beaver.h:31-70): `beaver_mask` before the
+open step, `beaver_finish` after it, one kernel launch each.  Plumbing only, like scl_amd itself: torch device buffers and the
+current HIP stream go to the C ABI; there is no CPU or torch fallback.  Tensors are those of scl_amd: int64 limbs, trailing
+dimension `limbs(field)`, a share matrix SoA `[party][secret][limb]` whose rows may sit a pitch apart.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import re
+
+import torch
+
+import scl_amd as _scl  # the engine first: libscl_hip_mpc.so links against libscl_hip.so and finds it loaded
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+_SO = os.path.join(_HERE, "libscl_hip_mpc.so")
+if not os.path.exists(_SO):
+    raise ImportError(
+        f"{_SO} is missing: build the HIP extension first "
+        "(python -c 'import __graft_entry__ as g; g.build()' or make -C secure-computation-library_amd/csrc)")
+lib = C.CDLL(_SO)
+
+
+def _declare_prototypes():
+    """argtypes / restype of every entry point from the prototypes of include/scl_hip_mpc.h, as scl_amd does for scl_hip.h;
+    the boundary's version is compared BEFORE any other symbol is looked up"""
+    candidates = [os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "scl_hip_mpc.h"), os.path.join(_HERE, "scl_hip_mpc.h")]
+    hdr = next((c for c in candidates if os.path.exists(c)), None)
+    if hdr is None:
+        raise ImportError("scl_amd.mpc: include/scl_hip_mpc.h not found beside the package")
+    src = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
+    want = re.search(r"#define\s+SCL_MPC_ABI_VERSION\s+(\d+)", src)
+    lib.scl_mpc_abi_version.restype = C.c_int
+    lib.scl_mpc_abi_version.argtypes = []
+    have = lib.scl_mpc_abi_version()
+    if not want or have != int(want.group(1)):
+        raise ImportError(f"scl_amd.mpc: {_SO} implements ABI version {have}, {hdr} declares {want.group(1) if want else '?'}: "
+                          "rebuild the extension (make -C secure-computation-library_amd/csrc)")
+    scalars = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "unsigned": C.c_uint}
+    rets = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+    n = 0
+    for m in re.finditer(r"\b(int|size_t|const char\s*\*)\s*(scl_mpc_\w+)\s*\(([^;{]*?)\)\s*;", src):
+        ret, name, params = m.group(1).replace(" ", "").replace("constchar*", "const char*"), m.group(2), m.group(3)
+        fn = getattr(lib, name)
+        fn.restype = rets[ret]
+        argt = []
+        for prm in [x.strip() for x in params.split(",")]:
+            if prm in ("void", ""):
+                continue
+            if "*" in prm or "[" in prm:
+                argt.append(C.c_void_p)
+            else:
+                base = re.sub(r"\bconst\b", "", prm).split()
+                if base[0] not in scalars:
+                    raise ImportError(f"scl_amd.mpc: {name}: parameter type {base[0]!r} in {hdr} has no ctypes mapping here")
+                argt.append(scalars[base[0]])
+        fn.argtypes = argt
+        n += 1
+    return n
+
+
+_NPROTO = _declare_prototypes()
+
+
+def _chk(status: int):
+    if status != _scl.OK:
+        raise _scl.SclError(status, lib.scl_mpc_last_error().decode())
+
+
+def _rows3(field, t: torch.Tensor, what: str):
+    """an operand as [rows][N][L]: a vector [N][L] is one row"""
+    L = _scl.limbs(field)
+    if t.dtype != torch.int64:
+        raise _scl.SclError(_scl.ERR_BAD_ARG, f"{what}: dtype {t.dtype}, expected int64 limbs")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.shape[2] != L:
+        raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{what}: shape {tuple(t.shape)}, expected [rows][N][{L}] or [N][{L}]")
+    return t
+
+
+def _same_rows(field, named):
+    """device pointers of operands that share one shape and one row stride"""
+    first_name, first = named[0]
+    ptrs, stride = [], None
+    for name, t in named:
+        if tuple(t.shape) != tuple(first.shape):
+            raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{name}: shape {tuple(t.shape)}, {first_name} has {tuple(first.shape)}")
+        if t.device != first.device:
+            raise _scl.SclError(_scl.ERR_BAD_ARG, f"{name}: on {t.device}, {first_name} on {first.device}")
+        p, s = _scl._dev_rows(t)
+        if stride is not None and s != stride:
+            raise _scl.SclError(_scl.ERR_BAD_ARG, f"{name}: row stride {s}, {first_name} has {stride} (operands share op_stride)")
+        stride = s
+        ptrs.append(p)
+    return ptrs, stride
+
+
+def beaver_mask(field, x, y, a, b, out=None):
+    """[e] = [x] - [a] and [d] = [y] - [b] in one launch (scl_mpc_beaver_mask).  Operands [rows][N][L] (or [N][L]: one row);
+    returns (e_rows, d_rows), the two halves of ONE tensor [2 rows][N][L] -- `out`, if given -- each shaped like the operands:
+    with one row the tensor is the reference's packet, e then d; with rows = n the halves go to shamir_recover /
+    additive_recover as they lie."""
+    vec = x.dim() == 2
+    ops = [(n, _rows3(field, t, "beaver_mask " + n)) for n, t in (("x", x), ("y", y), ("a", a), ("b", b))]
+    rows, N, L = ops[0][1].shape
+    ptrs, stride = _same_rows(field, ops)
+    if out is None:
+        out = torch.empty(2 * rows, N, L, dtype=torch.int64, device=x.device)
+    else:
+        _scl._want(out, (2 * rows, N, L), "beaver_mask out", x)
+    po, so = _scl._dev_rows(out)
+    _chk(lib.scl_mpc_beaver_mask(field, po, C.c_size_t(so), *ptrs, C.c_size_t(stride), C.c_size_t(rows), C.c_size_t(N), _scl._stream()))
+    return (out[0], out[1]) if vec else (out[:rows], out[rows:])
+
+
+def beaver_finish(field, e, d, a, b, c, ed_rows, out=None):
+    """[z] = e [b] + d [a] + [c], plus e d in the first `ed_rows` rows (scl_mpc_beaver_finish).  e, d: the opened values [N][L];
+    a, b, c: [rows][N][L] (or [N][L]: one row).  Shamir: ed_rows = rows; additive: 1 where row 0 is party 0, else 0.  `out` may be
+    a, b or c (in place)."""
+    vec = a.dim() == 2
+    ops = [(n, _rows3(field, t, "beaver_finish " + n)) for n, t in (("a", a), ("b", b), ("c", c))]
+    rows, N, L = ops[0][1].shape
+    _scl._want(e, (N, L), "beaver_finish e", a)
+    _scl._want(d, (N, L), "beaver_finish d", a)
+    ptrs, stride = _same_rows(field, ops)
+    if out is None:
+        z = torch.empty(rows, N, L, dtype=torch.int64, device=a.device)
+    else:
+        z = _rows3(field, out, "beaver_finish out")
+        _scl._want(z, (rows, N, L), "beaver_finish out", a)
+    pz, sz = _scl._dev_rows(z)
+    _chk(lib.scl_mpc_beaver_finish(field, pz, C.c_size_t(sz), _scl._dev(e), _scl._dev(d), *ptrs, C.c_size_t(stride), C.c_size_t(rows),
+                                   C.c_size_t(int(ed_rows)), C.c_size_t(N), _scl._stream()))
+    if out is not None:
+        return out
+    return z[0] if vec else z
