@@ -1,0 +1,498 @@
+// csrc/triples_unit.hip -- the trusted dealer of multiplication triples in the reference's PRG order: the kernels and the C ABI
+// of libscl_hip_prep.so (include/scl_hip_prep.h), an extension library beside the engine.  One translation unit, all fields.
+//
+// The reference deals a triple by randomTriple2 (test/scl/protocol/triple.h:37-48): a, b, then the sharings of a, of b and of
+// c = a b, all drawn from one util::PRG before the next triple begins.  Every PRG-driven entry point of the engine puts secret
+// s at counter0 + s * (its own block count), so no composition of them reaches that order; the AES blocks are counter-addressed,
+// though, so a lane that deals triple s encrypts the blocks [counter0 + s B, counter0 + (s+1) B) itself (the header states B
+// and the order of the draws).  Three kernels, all on the four-table AES of kernels.hpp (1024-lane workgroups, the 128 KiB of
+// tables at the bottom of 132 KiB of dynamic LDS, one workgroup per CU behind a grid-stride loop):
+//   k_triples_additive_prg  one lane = one triple (Mersenne61 on 16-byte bases and an even stride: two): B blocks, one product,
+//                           3 n row elements from three running differences
+//   k_triples_shamir_prg    one lane = one triple, the three polynomials one after another (at most t + 1 coefficients live),
+//                           the parties in a rolled loop, Horner at the small node i + 1 (F::muladd_small_lazy steps, one
+//                           F::canon at the end); one kernel per threshold 0..7
+//   k_triple_coeff_rows     the first of two passes: a, b, c and the 3 t coefficient rows into the caller's scratch; the engine's
+//                           explicit-coefficient scl_hip_shamir_share evaluates them (three calls)
+// None of them reads device memory.  The engine is reached through the prototypes of scl_hip.h only.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+
+#include "../../include/scl_hip_prep.h"
+#include "kernels.hpp"
+
+namespace sclhip {
+namespace {
+
+template <class F>
+constexpr int bpe() {  // FF::random burns ceil(byteSize/16) blocks (ff.h:72-76)
+  return F::LIMBS >= 2 ? F::LIMBS / 2 : 1;
+}
+
+// one FF::random at block c0: a one-limb element is the first 8 bytes of its block
+template <class F>
+__device__ __forceinline__ typename F::E draw_elem(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64 c0) {
+  constexpr int BPE = bpe<F>();
+  u64 lo[BPE], hi[BPE];
+#pragma unroll
+  for (int b = 0; b < BPE; ++b) aes.block(key, c0 + b, lo[b], hi[b]);
+  if constexpr (F::LIMBS == 1) return F::from_le_word(ctx, lo[0]);
+  else return elem_from_blocks<F>(ctx, lo, hi);
+}
+
+// additive: triple s = q*VEC + v at blocks counter0 + s*B, B = (2 + 3(n-1)) BPE; matrix m (0 a, 1 b, 2 c) draws its n-1 random
+// shares at element index 2 + m(n-1) + i of the triple, the last row is the secret minus their sum
+template <class F, int VEC>
+__global__ __launch_bounds__(ABLOCK) void k_triples_additive_prg(typename F::Ctx ctx, u64* a_out, u64* b_out, u64* c_out,
+                                                                 size_t stride, AesKey key, u64 counter0, int n, size_t npacks) {
+  SCL_AES4_PROLOGUE(key)
+  constexpr int BPE = bpe<F>();
+  const u64 B = (u64)(2 + 3 * (u64)(n - 1)) * BPE;
+  SCL_AES4_GRID_STRIDE(q, npacks) {
+    const size_t off = q * VEC * F::LIMBS;
+    Pack<F, VEC> last[3];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) {
+      const u64 c0 = counter0 + (q * VEC + v) * B;
+      last[0].v[v] = draw_elem<F>(ctx, aes, key, c0);
+      last[1].v[v] = draw_elem<F>(ctx, aes, key, c0 + BPE);
+      last[2].v[v] = F::mul(ctx, last[0].v[v], last[1].v[v]);
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      u64* out = (m == 0 ? a_out : m == 1 ? b_out : c_out) + off;
+#pragma unroll 1
+      for (int i = 0; i + 1 < n; ++i) {
+        Pack<F, VEC> r;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+          r.v[v] = draw_elem<F>(ctx, aes, key, counter0 + (q * VEC + v) * B + (u64)(2 + (u64)m * (n - 1) + i) * BPE);
+          last[m].v[v] = F::sub(ctx, last[m].v[v], r.v[v]);
+        }
+        store_pack<F, VEC, true>(out + (size_t)i * stride * F::LIMBS, r);
+      }
+      store_pack<F, VEC, true>(out + (size_t)(n - 1) * stride * F::LIMBS, last[m]);
+    }
+  }
+}
+
+// Blocks of one Vector::random(t+1) draw
+template <class F>
+__host__ __device__ inline u64 poly_blocks(u64 t) {
+  return ((t + 1) * (u64)(8 * F::LIMBS) + 15) / 16;
+}
+
+// coefficients 1..T of the polynomial whose Vector::random(T+1) draw starts at block p0 (element 0 is discarded, shamir.h:57):
+// one-limb fields hold elements 2j and 2j+1 in block j, wider ones element k in blocks k*BPE ..
+template <class F, int T>
+__device__ __forceinline__ void draw_poly(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64 p0,  // (by value)
+                                          typename F::E (&c)[T + 1]) {
+  if constexpr (F::LIMBS == 1) {
+#pragma unroll
+    for (int j = 0; 2 * j <= T; ++j) {
+      u64 lo, hi;
+      aes.block(key, p0 + j, lo, hi);
+      if (j > 0) c[2 * j] = F::from_le_word(ctx, lo);
+      if (2 * j + 1 <= T) c[2 * j + 1] = F::from_le_word(ctx, hi);
+    }
+  } else {
+    constexpr int BPE = bpe<F>();
+#pragma unroll
+    for (int k = 1; k <= T; ++k) {
+      u64 lo[BPE], hi[BPE];
+#pragma unroll
+      for (int b = 0; b < BPE; ++b) aes.block(key, p0 + (u64)k * BPE + b, lo[b], hi[b]);
+      c[k] = elem_from_blocks<F>(ctx, lo, hi);
+      // one coefficient's blocks at a time: left alone the compiler runs all T draws abreast (some ten registers each) and
+      // runs out of the 128 a 1024-lane workgroup has.  The empty statement makes the next counter wait for this result.
+#if defined(__HIP_DEVICE_COMPILE__)
+      asm volatile("" : "+v"(p0) : "v"((u32)lo[0]));
+#endif
+    }
+  }
+}
+
+// every triple of the launch at threshold T: the three polynomials one after another, the parties in a rolled loop
+template <class F, int T>
+__device__ __forceinline__ void deal_shamir(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64* a_out, u64* b_out,
+                                            u64* c_out, size_t stride, u64 counter0, int n, size_t N) {
+  constexpr int BPE = bpe<F>();
+  constexpr u64 Bs = ((u64)(T + 1) * 8 * F::LIMBS + 15) / 16, B = 2 * BPE + 3 * Bs;
+  SCL_AES4_GRID_STRIDE(s, N) {
+    const u64 c0 = counter0 + s * B;
+    const typename F::E a = draw_elem<F>(ctx, aes, key, c0), b = draw_elem<F>(ctx, aes, key, c0 + BPE);
+    const typename F::E ab = F::mul(ctx, a, b);
+#pragma unroll 1
+    for (int m = 0; m < 3; ++m) {
+      typename F::E c[T + 1];
+      c[0] = m == 0 ? a : m == 1 ? b : ab;
+      draw_poly<F, T>(ctx, aes, key, c0 + 2 * BPE + (u64)m * Bs, c);
+      u64* out = (m == 0 ? a_out : m == 1 ? b_out : c_out) + s * F::LIMBS;
+#pragma unroll 1
+      for (int i = 0; i < n; ++i) {
+        const u32 x = (u32)(i + 1);
+        typename F::E y = c[T];
+#pragma unroll
+        for (int k = T; k >= 1; --k) y = F::muladd_small_lazy(ctx, y, x, c[k - 1]);  // congruent, not yet canonical
+        y = F::canon(y);
+        Pack<F, 1> r;
+        r.v[0] = y;
+        store_pack<F, 1, true>(out + (size_t)i * stride * F::LIMBS, r);
+      }
+    }
+  }
+}
+
+// Shamir, fused: triple s at blocks counter0 + s*B, B = 2 BPE + 3 Bs.  One kernel per threshold T, so that the coefficients
+// stay in registers and Horner has no tests in it.  Fields with F::muladd_small_lazy (the Mersenne fields, GF(2^128)): node
+// i+1 < 2^16.
+template <class F, int T>
+__global__ __launch_bounds__(ABLOCK) void k_triples_shamir_prg(typename F::Ctx ctx, u64* a_out, u64* b_out, u64* c_out,
+                                                               size_t stride, AesKey key, u64 counter0, int n, size_t N) {
+  SCL_AES4_PROLOGUE(key)
+  deal_shamir<F, T>(ctx, aes, key, a_out, b_out, c_out, stride, counter0, n, N);
+}
+
+// Two-pass, first pass: rows 0, 1, 2 of the scratch are a, b, c = a b; row 3 + m t + (k-1) is coefficient k of polynomial m.
+// Rows are N elements apart.
+template <class F>
+__global__ __launch_bounds__(ABLOCK) void k_triple_coeff_rows(typename F::Ctx ctx, u64* rows, AesKey key, u64 counter0, int t,
+                                                              size_t N) {
+  SCL_AES4_PROLOGUE(key)
+  constexpr int BPE = bpe<F>();
+  const u64 Bs = poly_blocks<F>((u64)t), B = 2 * BPE + 3 * Bs;
+  SCL_AES4_GRID_STRIDE(s, N) {
+    const u64 c0 = counter0 + s * B;
+    const typename F::E a = draw_elem<F>(ctx, aes, key, c0), b = draw_elem<F>(ctx, aes, key, c0 + BPE);
+    F::st(rows + s * F::LIMBS, a);
+    F::st(rows + (N + s) * F::LIMBS, b);
+    F::st(rows + (2 * N + s) * F::LIMBS, F::mul(ctx, a, b));
+#pragma unroll 1
+    for (int m = 0; m < 3; ++m) {
+      const u64 p0 = c0 + 2 * BPE + (u64)m * Bs;
+      u64* base = rows + ((size_t)(3 + (size_t)m * t) * N + s) * F::LIMBS;  // coefficient 1 of polynomial m
+      if constexpr (F::LIMBS == 1) {
+#pragma unroll 1
+        for (int j = 0; 2 * j <= t; ++j) {  // block j = coefficients 2j (low 8 bytes) and 2j+1 (high 8 bytes)
+          u64 lo, hi;
+          aes.block(key, p0 + j, lo, hi);
+          if (j > 0) base[(size_t)(2 * j - 1) * N] = F::from_le_word(ctx, lo);
+          if (2 * j + 1 <= t) base[(size_t)(2 * j) * N] = F::from_le_word(ctx, hi);
+        }
+      } else {
+#pragma unroll 1
+        for (int k = 1; k <= t; ++k) {
+          u64 lo[BPE], hi[BPE];
+#pragma unroll
+          for (int bb = 0; bb < BPE; ++bb) aes.block(key, p0 + (u64)k * BPE + bb, lo[bb], hi[bb]);
+          F::st(base + (size_t)(k - 1) * N * F::LIMBS, elem_from_blocks<F>(ctx, lo, hi));
+        }
+      }
+    }
+  }
+}
+
+}  // namespace
+}  // namespace sclhip
+
+// ---- the entry points ------------------------------------------------------------------------------------------------------
+namespace {
+using namespace sclhip;
+
+constexpr size_t FUSED_TMAX = 7;        // the fused Shamir kernel keeps t + 1 <= 8 coefficients in registers
+constexpr size_t PARTY_MAX = 65535;     // Shamir: the node i + 1 as a small integer (GF(2^128): F::muladd_small takes 16 bits)
+// The largest threshold the two-pass path takes: beyond it scl_hip_shamir_share evaluates chunk by chunk, staging each chunk's
+// power table from host memory and synchronising the stream before it returns -- a call of this library never synchronises
+constexpr size_t T_MAX_NARROW = 48;     // 8- and 16-byte elements
+constexpr size_t T_MAX_WIDE = 16;       // 32-byte elements
+
+thread_local std::string g_err;  // the thread's last diagnostic of THIS library
+
+int fail(int code, const std::string& msg) {
+  g_err = msg;
+  return code;
+}
+#define HIP_TRY(expr)                                                                                                        \
+  do {                                                                                                                       \
+    hipError_t e_ = (expr);                                                                                                  \
+    if (e_ != hipSuccess)                                                                                                    \
+      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+  } while (0)
+
+inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
+
+unsigned grid_aes4(size_t work_items) {  // one 1024-lane workgroup per CU; the kernels grid-stride
+  const size_t blocks = (work_items + ABLOCK - 1) / ABLOCK;
+  return (unsigned)(blocks < 1 ? 1 : blocks > (size_t)AES4_GRID_CAP ? (size_t)AES4_GRID_CAP : blocks);
+}
+#define AES4_LAUNCH(KERN, WORK, ST, ...)                                                                            \
+  do {                                                                                                              \
+    auto kern_ = &KERN;                                                                                             \
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,   \
+                                AES4_LDS_BYTES));                                                                   \
+    hipLaunchKernelGGL(kern_, dim3(grid_aes4(WORK)), dim3(ABLOCK), AES4_LDS_BYTES, ST, __VA_ARGS__);                \
+    HIP_TRY(hipGetLastError());                                                                                     \
+  } while (0)
+
+// The AES-128 key schedule of the reference's PRG (prg.cc:88-101: key = the seed zero-padded or truncated to 16 bytes) and the
+// T-table the kernels replicate in LDS: te0[x] = (2S, S, S, 3S) from byte 0 up, S = sbox[x].  FIPS-197; the S-box from its
+// definition (inverse in GF(2^8) through the logarithms to the generator 3, then the affine map).
+struct Sbox {
+  unsigned char s[256];
+  Sbox() {
+    auto xt = [](unsigned a) { return ((a << 1) ^ ((a & 0x80) ? 0x11b : 0)) & 0xff; };
+    unsigned char ex[256], lg[256] = {0};
+    unsigned v = 1;
+    for (int i = 0; i < 255; ++i) {
+      ex[i] = (unsigned char)v;
+      lg[v] = (unsigned char)i;
+      v ^= xt(v);  // v * 3
+    }
+    for (int x = 0; x < 256; ++x) {
+      const unsigned inv = x ? ex[(255 - lg[x]) % 255] : 0;
+      unsigned r = inv, rot = inv;
+      for (int i = 0; i < 4; ++i) {
+        rot = ((rot << 1) | (rot >> 7)) & 0xff;
+        r ^= rot;
+      }
+      s[x] = (unsigned char)(r ^ 0x63);
+    }
+  }
+};
+
+void make_aes_key(const unsigned char* seed, size_t seed_len, AesKey& k) {
+  static const Sbox sb;
+  unsigned char rk[176] = {0};
+  if (seed) std::memcpy(rk, seed, seed_len > 16 ? 16 : seed_len);
+  unsigned rcon = 1;
+  for (int i = 16; i < 176; i += 4) {
+    unsigned char w[4] = {rk[i - 4], rk[i - 3], rk[i - 2], rk[i - 1]};
+    if (i % 16 == 0) {
+      const unsigned char w0 = w[0];
+      w[0] = (unsigned char)(sb.s[w[1]] ^ rcon);
+      w[1] = sb.s[w[2]];
+      w[2] = sb.s[w[3]];
+      w[3] = sb.s[w0];
+      rcon = ((rcon << 1) ^ ((rcon & 0x80) ? 0x11b : 0)) & 0xff;
+    }
+    for (int j = 0; j < 4; ++j) rk[i + j] = (unsigned char)(rk[i - 16 + j] ^ w[j]);
+  }
+  for (int w = 0; w < 44; ++w)
+    k.rk[w] = (u32)rk[4 * w] | ((u32)rk[4 * w + 1] << 8) | ((u32)rk[4 * w + 2] << 16) | ((u32)rk[4 * w + 3] << 24);
+  for (int x = 0; x < 256; ++x) {
+    const unsigned s = sb.s[x], s2 = ((s << 1) ^ ((s & 0x80) ? 0x11b : 0)) & 0xff, s3 = s2 ^ s;
+    k.te0[x] = s2 | (s << 8) | (s << 16) | (s3 << 24);
+  }
+  aes_key_round1(k);
+}
+
+// the calling thread's Mont128 parameters, behind the engine's stale-latch check (reached through scl_hip_lagrange_basis on one
+// node, a host-only call, as csrc/beaver_unit.hip does and tests/test_prep_abi.py pins from this side)
+int mont_ctx(Mont128::Ctx& out) {
+  uint64_t one_node[2];
+  const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
+  if (rc != SCL_OK) return fail(rc, scl_hip_last_error());
+  uint64_t p[2];
+  scl_hip_mont128_get_prime(p);
+  static thread_local Mont128::Ctx cached = {0, 0, 0, 0, 0, 0};
+  const u128 prime = ((u128)p[1] << 64) | p[0];
+  if (cached.p != prime) cached = Mont128::make_ctx(prime);
+  out = cached;
+  return SCL_OK;
+}
+
+// the latch rule comes first among a call's checks, as in the engine: a stale thread learns of it whatever else is wrong
+int mont_latch(int field) {
+  Mont128::Ctx ctx;
+  return field == SCL_MONT128 ? mont_ctx(ctx) : SCL_OK;
+}
+
+bool is_ring(int field) { return field > 0x100 && field <= 0x100 + 128; }
+bool is_field(int field) { return field >= SCL_M61 && field <= SCL_SECP256K1_FIELD; }
+size_t limbs_of(int field) {  // 0: unknown tag
+  if (is_ring(field)) return field - 0x100 <= 64 ? 1 : 2;
+  switch (field) {
+    case SCL_M61: return 1;
+    case SCL_M127: case SCL_MONT128: case SCL_GF2_128: return 2;
+    case SCL_SECP256K1_SCALAR: case SCL_SECP256K1_FIELD: return 4;
+    default: return 0;
+  }
+}
+size_t bpe_of(size_t limbs) { return limbs >= 2 ? limbs / 2 : 1; }
+
+template <class Fn>
+int with_field(int field, Fn&& fn) {
+  switch (field) {
+    case SCL_M61: return fn(M61{}, M61::Ctx{});
+    case SCL_M127: return fn(M127{}, M127::Ctx{});
+    case SCL_MONT128: {
+      Mont128::Ctx ctx;
+      const int rc = mont_ctx(ctx);
+      if (rc != SCL_OK) return rc;
+      return fn(Mont128{}, ctx);
+    }
+    case SCL_GF2_128: return fn(Gf128{}, Gf128::Ctx{});
+    case SCL_SECP256K1_SCALAR: return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
+    case SCL_SECP256K1_FIELD: return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
+    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+  }
+}
+template <class Fn>
+int with_ring_or_field(int field, Fn&& fn) {
+  if (is_ring(field)) {
+    const int K = field - 0x100;
+    if (K <= 64) return fn(Z2k64{}, Z2k64::make_ctx(K));
+    return fn(Z2k128{}, Z2k128::make_ctx(K));
+  }
+  return with_field(field, fn);
+}
+
+bool fused_shamir(int field, size_t t, unsigned flags) {
+  return !(flags & SCL_PREP_TWO_PASS) && t <= FUSED_TMAX && (field == SCL_M61 || field == SCL_M127 || field == SCL_GF2_128);
+}
+
+size_t additive_blocks(size_t limbs, size_t n) { return (2 + 3 * (n - 1)) * bpe_of(limbs); }
+size_t shamir_blocks(size_t limbs, size_t t) { return 2 * bpe_of(limbs) + 3 * (((t + 1) * 8 * limbs + 15) / 16); }
+bool additive_n_ok(size_t n) { return n >= 2 && n <= 0x7fffffffu / 4; }
+size_t shamir_t_max(size_t limbs) { return limbs == 4 ? T_MAX_WIDE : T_MAX_NARROW; }
+bool shamir_nt_ok(size_t limbs, size_t n, size_t t) { return n >= 1 && n <= PARTY_MAX && t <= shamir_t_max(limbs); }
+
+struct Span {  // the words a matrix of `rows` rows of N elements, `stride` elements apart, covers: [lo, hi)
+  const uint64_t *lo, *hi;
+};
+Span span_of(const uint64_t* p, size_t rows, size_t stride, size_t N, size_t limbs) { return {p, p + ((rows - 1) * stride + N) * limbs}; }
+bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
+
+// what both deal calls check alike, in the order the header lists it; B = blocks per triple
+int check_matrices(const char* who, size_t limbs, uint64_t* a, uint64_t* b, uint64_t* c, size_t stride, size_t N, size_t n, uint64_t B,
+                   uint64_t counter0) {
+  const std::string w(who);
+  if (!a || !b || !c) return fail(SCL_ERR_BAD_ARG, w + ": NULL operand");
+  const uintptr_t mask = limbs == 1 ? 7 : 15;
+  for (const uint64_t* p : {a, b, c})
+    if (reinterpret_cast<uintptr_t>(p) & mask)
+      return fail(SCL_ERR_BAD_ARG, w + (limbs == 1 ? ": pointer not 8-byte aligned" : ": pointer not 16-byte aligned"));
+  if (stride < N) return fail(SCL_ERR_SIZE_MISMATCH, w + ": stride < N");
+  if (n > ((size_t)1 << 60) / stride / limbs) return fail(SCL_ERR_BAD_ARG, w + ": n * stride overflows");
+  const Span sa = span_of(a, n, stride, N, limbs), sb = span_of(b, n, stride, N, limbs), sc = span_of(c, n, stride, N, limbs);
+  if (overlap(sa, sb) || overlap(sa, sc) || overlap(sb, sc)) return fail(SCL_ERR_BAD_ARG, w + ": the share matrices overlap");
+  // N * B blocks from counter0 (and the slack aes_key_range adds) must not wrap the 64-bit counter
+  const uint64_t room = ~(uint64_t)0 - 128;
+  if (counter0 > room || N > (room - counter0) / B) return fail(SCL_ERR_BAD_ARG, w + ": the block range wraps the 64-bit counter");
+  return SCL_OK;
+}
+
+int need_device() {
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  return SCL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int scl_prep_abi_version(void) { return SCL_PREP_ABI_VERSION; }
+const char* scl_prep_last_error(void) { return g_err.c_str(); }
+
+size_t scl_prep_triple_blocks(int field, int scheme, size_t n, size_t t) {
+  const size_t L = limbs_of(field);
+  if (scheme == SCL_PREP_ADDITIVE) return L && additive_n_ok(n) ? additive_blocks(L, n) : 0;
+  if (scheme == SCL_PREP_SHAMIR) return is_field(field) && shamir_nt_ok(L, n, t) ? shamir_blocks(L, t) : 0;
+  return 0;
+}
+
+size_t scl_prep_triples_scratch_bytes(int field, size_t N, size_t n, size_t t, unsigned flags) {
+  if (!is_field(field) || !shamir_nt_ok(limbs_of(field), n, t) || (flags & ~SCL_PREP_TWO_PASS) || fused_shamir(field, t, flags)) return 0;
+  const size_t per = (3 + 3 * t) * 8 * limbs_of(field);
+  return N > ((size_t)1 << 62) / per ? 0 : N * per;
+}
+
+int scl_prep_triples_additive_prg(int field, uint64_t* a_dev, uint64_t* b_dev, uint64_t* c_dev, size_t stride, size_t N, size_t n,
+                                  const unsigned char* seed_host, size_t seed_len, uint64_t counter0, void* stream) {
+  if (N == 0) return SCL_OK;
+  const size_t L = limbs_of(field);
+  if (!L) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+  if (const int rc = mont_latch(field)) return rc;
+  if (!additive_n_ok(n)) return fail(SCL_ERR_BAD_ARG, "triples_additive_prg: n must be >= 2 (and below 2^29)");
+  const uint64_t B = additive_blocks(L, n);
+  if (const int rc = check_matrices("triples_additive_prg", L, a_dev, b_dev, c_dev, stride, N, n, B, counter0)) return rc;
+  return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
+    using F = decltype(f);
+    if (const int rc = need_device()) return rc;
+    AesKey key;
+    make_aes_key(seed_host, seed_len, key);
+    aes_key_range(key, counter0, (u64)N * B);
+    // two one-limb triples per lane: 16-byte aligned bases and an even stride; an odd N leaves one triple to a launch of its own
+    bool two = F::LIMBS == 1 && !(stride & 1);
+    for (const uint64_t* p : {a_dev, b_dev, c_dev}) two = two && !(reinterpret_cast<uintptr_t>(p) & 15);
+    size_t first = 0;
+    if constexpr (F::LIMBS == 1) {
+      if (two && N >= 2) {
+        AES4_LAUNCH((k_triples_additive_prg<F, 2>), N / 2, S(stream), ctx, a_dev, b_dev, c_dev, stride, key, (u64)counter0, (int)n, N / 2);
+        first = N & ~(size_t)1;
+      }
+    }
+    if (first < N)
+      AES4_LAUNCH((k_triples_additive_prg<F, 1>), N - first, S(stream), ctx, a_dev + first * F::LIMBS, b_dev + first * F::LIMBS,
+                  c_dev + first * F::LIMBS, stride, key, (u64)(counter0 + first * B), (int)n, N - first);
+    return SCL_OK;
+  });
+}
+
+int scl_prep_triples_shamir_prg(int field, uint64_t* a_dev, uint64_t* b_dev, uint64_t* c_dev, size_t stride, size_t N, size_t t,
+                                size_t n, const unsigned char* seed_host, size_t seed_len, uint64_t counter0, uint64_t* scratch_dev,
+                                unsigned flags, void* stream) {
+  if (N == 0) return SCL_OK;
+  if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+  if (const int rc = mont_latch(field)) return rc;
+  if (flags & ~SCL_PREP_TWO_PASS) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: unknown flags bit (only bit 0, two-pass, is defined)");
+  const size_t L = limbs_of(field);
+  if (!shamir_nt_ok(L, n, t))
+    return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: n must be in 1..65535 and the threshold t at most " + std::to_string(shamir_t_max(L)) +
+                                     " for this field (beyond it the engine's share call synchronises the stream)");
+  const uint64_t B = shamir_blocks(L, t);
+  if (const int rc = check_matrices("triples_shamir_prg", L, a_dev, b_dev, c_dev, stride, N, n, B, counter0)) return rc;
+  const bool fused = fused_shamir(field, t, flags);
+  if (!fused) {
+    const size_t need = scl_prep_triples_scratch_bytes(field, N, n, t, flags);
+    if (!need) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: (3 + 3t) * N overflows");
+    if (!scratch_dev)
+      return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: this case takes the two-pass path and needs " + std::to_string(need) +
+                                       " bytes of scratch (scl_prep_triples_scratch_bytes); scratch_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: scratch pointer not 16-byte aligned");
+    const Span ss = {scratch_dev, scratch_dev + need / 8};
+    for (const uint64_t* p : {a_dev, b_dev, c_dev})
+      if (overlap(ss, span_of(p, n, stride, N, L))) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: the scratch overlaps a share matrix");
+  }
+  return with_field(field, [&](auto f, auto ctx) -> int {
+    using F = decltype(f);
+    if (const int rc = need_device()) return rc;
+    AesKey key;
+    make_aes_key(seed_host, seed_len, key);
+    aes_key_range(key, counter0, (u64)N * B);
+    if constexpr (F::TAG == 0 || F::TAG == 1 || F::TAG == 3) {
+      if (fused) {
+#define TRIPLES_CASE(TT) \
+  case TT: AES4_LAUNCH((k_triples_shamir_prg<F, TT>), N, S(stream), ctx, a_dev, b_dev, c_dev, stride, key, (u64)counter0, (int)n, N); break;
+        switch (t) {
+          TRIPLES_CASE(0) TRIPLES_CASE(1) TRIPLES_CASE(2) TRIPLES_CASE(3) TRIPLES_CASE(4) TRIPLES_CASE(5) TRIPLES_CASE(6) TRIPLES_CASE(7)
+          default: return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: internal threshold");
+        }
+#undef TRIPLES_CASE
+        return SCL_OK;
+      }
+    }
+    AES4_LAUNCH((k_triple_coeff_rows<F>), N, S(stream), ctx, scratch_dev, key, (u64)counter0, (int)t, N);
+    uint64_t* outs[3] = {a_dev, b_dev, c_dev};
+    for (size_t m = 0; m < 3; ++m) {
+      const uint64_t* coeffs = t ? scratch_dev + (3 + m * t) * N * F::LIMBS : nullptr;
+      const int rc = scl_hip_shamir_share(field, outs[m], stride, scratch_dev + m * N * F::LIMBS, coeffs, t ? N : 0, N, t, n, nullptr, stream);
+      if (rc != SCL_OK) return fail(rc, std::string("triples_shamir_prg: scl_hip_shamir_share: ") + scl_hip_last_error());
+    }
+    return SCL_OK;
+  });
+}
+
+}  // extern "C"
