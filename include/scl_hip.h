@@ -30,6 +30,19 @@
  *    a caller pass a window of a larger matrix (sharding, chunking).  An AoS
  *    [secret][party] image (the reference's Vector per secret) converts with
  *    scl_hip_aos_to_soa / scl_hip_soa_to_aos.
+ *  - aliasing: an output may COINCIDE with an input only where the entry point
+ *    says so ("x_dev may be y_dev" in its comment); coincide means the same
+ *    pointer and, for matrices, the same stride.  Any other overlap -- of an
+ *    output with an input, of two outputs with each other, of caller scratch
+ *    with anything -- is SCL_ERR_BAD_ARG; scl_hip_last_error() names both
+ *    operands, and the call refuses before anything is launched or written.
+ *    Overlap is judged on bounding spans,
+ *    [ptr, ptr + ((rows - 1) * stride + cols) * element bytes), gaps between
+ *    the rows of a pitched matrix included (include/scl_hip/detail/span.hpp);
+ *    an extent that does not fit size_t is refused the same way, never
+ *    wrapped.  Empty operands (n == 0, rows == 0, a NULL pointer where one is
+ *    allowed) overlap nothing; two inputs may always share memory.  Host
+ *    pointers are outside the rule.
  *  - stream is a hipStream_t passed as void* (NULL = the default stream);
  *    calls are asynchronous w.r.t. the host unless they return a host value or
  *    must report a data-dependent error (documented per function).
@@ -147,10 +160,11 @@ int scl_hip_thread_cleanup(void);
 
 /* ---- element-wise: scl::math::Vector<FF> members ------------------------- */
 /* Vector::add / subtract / multiplyEntryWise (+InPlace) (vector.h:199-245,521-556),
- * FF::negate / invert / operator/ per element (ff.h:203-246).  dst may alias a or b.
+ * FF::negate / invert / operator/ per element (ff.h:203-246).
  * b is ignored for NEG and INV.  INV and DIV are synchronous: a zero operand yields
  * SCL_ERR_ZERO_INVERSE after the launch completes (the reference throws at the
  * first zero; here every other element is still computed, the slot of a zero -- of an even element, in a ring -- gets 0). */
+/* Aliasing: dst_dev may be a_dev; dst_dev may be b_dev (and a_dev may be b_dev: two inputs; all three may be one buffer). */
 int scl_hip_ew(int field, int op, uint64_t* dst_dev, const uint64_t* a_dev, const uint64_t* b_dev,
                size_t n, void* stream);
 /* The same call, asynchronous for every op: the "an operand was not invertible" report of INV / DIV (the reference's throw,
@@ -160,9 +174,12 @@ int scl_hip_ew(int field, int op, uint64_t* dst_dev, const uint64_t* a_dev, cons
  * scl_hip_memset / hipMemsetAsync on the same stream, read it whenever the caller synchronises anyway (cf. the status vector of
  * scl_hip_shamir_recover_detect).  No host synchronisation, no host read: small batches do not pay a stream round trip and the
  * call can be captured into a hipGraph.  status_dev may be NULL for ops that cannot fail (ADD, SUB, MUL, NEG). */
+/* Aliasing: status_dev must not overlap any other operand; dst_dev may be a_dev; dst_dev may be b_dev (and a_dev may be
+ * b_dev, as for scl_hip_ew). */
 int scl_hip_ew_status(int field, int op, uint64_t* dst_dev, const uint64_t* a_dev, const uint64_t* b_dev,
                       size_t n, unsigned* status_dev, void* stream);
 /* Vector::scalarMultiply(InPlace) (vector.h:274-301): dst[i] = scalar * a[i] */
+/* Aliasing: dst_dev may be a_dev. */
 int scl_hip_scalar_mul(int field, uint64_t* dst_dev, const uint64_t* a_dev,
                        const uint64_t* scalar_host, size_t n, void* stream);
 /* Vector::sum (vector.h:261-267) and Vector::dot / innerProd (vector.h:45-52,252-255);
@@ -178,14 +195,19 @@ int scl_hip_equals(int field, int* equal_host, const uint64_t* a_dev, const uint
 /* PRG::next as a counter-addressed stream (src/scl/util/prg.cc:124-146): writes
  * nblocks*16 bytes, block i = AES128_key(LE64(counter0+i) || LE64(PRG_NONCE)), key = seed
  * zero-padded / truncated to 16 bytes (prg.cc:88-101). */
+/* Aliasing: dst_dev is the only device operand. */
 int scl_hip_prg_blocks(unsigned char* dst_dev, size_t nblocks, const unsigned char* seed_host,
                        size_t seed_len, uint64_t counter0, void* stream);
 /* FF::read / ff::fromBytes (mersenne61.cc:86-90, mersenne127.cc:114-118): n elements from
  * n*byteSize raw bytes, reduced mod p. */
+/* Aliasing: dst_dev may be src_dev where byteSize is the element's size in memory -- every field, and the rings of 57..64
+ * and of 121..128 bits: element i is read from the bytes it is written to --; a narrower ring packs its bytes tighter than
+ * its elements, and there, as for any other overlap, the call is refused. */
 int scl_hip_from_bytes(int field, uint64_t* dst_dev, const unsigned char* src_dev, size_t n,
                        void* stream);
 /* Vector::random(n, prg) for a PRG whose counter stands at counter0 (vector.h:507-519):
  * consumes ceil(n*byteSize/16) blocks. */
+/* Aliasing: dst_dev is the only device operand. */
 int scl_hip_vector_random(int field, uint64_t* dst_dev, size_t n, const unsigned char* seed_host,
                           size_t seed_len, uint64_t counter0, void* stream);
 
@@ -199,6 +221,7 @@ int scl_hip_lagrange_basis(int field, uint64_t* lambda_host, const uint64_t* alp
 /* Batched shamirSecretShare (include/scl/ss/shamir.h:51-68) with explicit coefficients:
  * shares[i][s] = secrets[s] + sum_{k=1..t} coeffs[k-1][s] * alpha_i^k for i < n.
  * coeffs is SoA [t][N] with row stride coeff_stride; alphas_host NULL = 1..n. */
+/* Aliasing: shares_dev must not overlap any other operand. */
 int scl_hip_shamir_share(int field, uint64_t* shares_dev, size_t share_stride,
                          const uint64_t* secrets_dev, const uint64_t* coeffs_dev,
                          size_t coeff_stride, size_t N, size_t t, size_t n,
@@ -209,6 +232,7 @@ int scl_hip_shamir_share(int field, uint64_t* shares_dev, size_t share_stride,
  * [counter0 + s*B, counter0 + (s+1)*B), B = ceil((t+1)*byteSize/16); the draw for c_0 is made and
  * discarded, shamir.h:56-57).  A shard that starts at secret index f of a longer run passes
  * counter0 = f*B.  The PRG has consumed N*B blocks afterwards. */
+/* Aliasing: shares_dev must not overlap secrets_dev. */
 int scl_hip_shamir_share_prg(int field, uint64_t* shares_dev, size_t share_stride,
                              const uint64_t* secrets_dev, size_t N, size_t t, size_t n,
                              const unsigned char* seed_host, size_t seed_len,
@@ -220,12 +244,14 @@ int scl_hip_shamir_share_prg(int field, uint64_t* shares_dev, size_t share_strid
  * shares_dev + (j * n + i) * share_stride elements.  Secret s starts at block counter0 + s * ceil((t+1)*W*byteSize/16).
  * The EC commitments are calls of their own over this layout: scl_hip_feldman_commit for a width of one,
  * scl_hip_pedersen_commit for the {secret, blinding} pairs of width = 2. */
+/* Aliasing: shares_dev must not overlap secrets_dev. */
 int scl_hip_shamir_share_prg_packed(int field, uint64_t* shares_dev, size_t share_stride, const uint64_t* secrets_dev,
                                     size_t secret_stride, size_t N, size_t t, size_t n, size_t width,
                                     const unsigned char* seed_host, size_t seed_len, uint64_t counter0, void* stream);
 /* Batched shamirRecoverP (shamir.h:81-104) with the basis hoisted out of the per-secret
  * call: out[s] = sum_{i<m} lambda[i] * shares[i][s].  Asynchronous like the other batch calls, the
  * first call of a process included (GF(2^128) too: no first-use work), so it can be captured into a hipGraph. */
+/* Aliasing: out_dev must not overlap shares_dev. */
 int scl_hip_shamir_recover(int field, uint64_t* out_dev, const uint64_t* shares_dev,
                            size_t share_stride, const uint64_t* lambda_host, size_t m, size_t N,
                            void* stream);
@@ -234,6 +260,7 @@ int scl_hip_shamir_recover(int field, uint64_t* out_dev, const uint64_t* shares_
  * reference would throw "error detected during recovery" (out[s] = 0 there).
  * Synchronous; returns SCL_ERR_ERROR_DETECTED if any status is set, with
  * *num_bad_host = how many.  alphas_host NULL = 1..m, x_host NULL = 0. */
+/* Aliasing: out_dev must not overlap any other operand; status_dev must not overlap any other operand. */
 int scl_hip_shamir_recover_detect(int field, uint64_t* out_dev, unsigned char* status_dev,
                                   const uint64_t* shares_dev, size_t share_stride, size_t m,
                                   size_t N, size_t t, size_t d, const uint64_t* alphas_host,
@@ -251,6 +278,8 @@ int scl_hip_shamir_recover_detect(int field, uint64_t* out_dev, unsigned char* s
  * queued and solved one workgroup each (one wavefront up to 64 shares; the systems in LDS while they fit, in device
  * memory beyond that).  Synchronous.  *num_queued_host = secrets that needed the solver,
  * *num_failed_host = how many of them could not be corrected (either may be NULL).  alphas_host NULL = 1..n. */
+/* Aliasing: f_dev must not overlap any other operand; e_dev must not overlap any other operand; status_dev must not overlap
+ * any other operand; nerr_dev must not overlap any other operand. */
 int scl_hip_shamir_recover_correct(int field, uint64_t* f_dev, size_t f_stride, uint64_t* e_dev, size_t e_stride,
                                    unsigned char* status_dev, unsigned* nerr_dev, const uint64_t* shares_dev,
                                    size_t share_stride, size_t m, size_t N, const uint64_t* alphas_host,
@@ -259,32 +288,41 @@ int scl_hip_shamir_recover_correct(int field, uint64_t* f_dev, size_t f_stride, 
 /* ---- additive: scl::ss::additiveShare, Vector::sum ------------------------ */
 /* additiveShare (include/scl/ss/additive.h:41-53) with explicit randomness rnd [n-1][N]:
  * shares[i] = rnd[i] for i < n-1, shares[n-1] = secret - sum. */
+/* Aliasing: shares_dev must not overlap secrets_dev; shares_dev may be rnd_dev (with rnd_stride == share_stride: the
+ * randomness already sits in rows 0 .. n-2 of the share matrix and row n-1 is filled in). */
 int scl_hip_additive_share(int field, uint64_t* shares_dev, size_t share_stride,
                            const uint64_t* secrets_dev, const uint64_t* rnd_dev, size_t rnd_stride,
                            size_t N, size_t n, void* stream);
 /* PRG-driven: share i < n-1 of secret s is FF::random on block counter0 + s*(n-1) + i (one whole
  * AES block per element, ff.h:72-76); N*(n-1) blocks are consumed. */
+/* Aliasing: shares_dev must not overlap secrets_dev. */
 int scl_hip_additive_share_prg(int field, uint64_t* shares_dev, size_t share_stride,
                                const uint64_t* secrets_dev, size_t N, size_t n,
                                const unsigned char* seed_host, size_t seed_len,
                                uint64_t counter0, void* stream);
 /* reconstruct = Vector::sum per secret (vector.h:261-267): out[s] = sum_i shares[i][s] */
+/* Aliasing: out_dev must not overlap shares_dev. */
 int scl_hip_additive_recover(int field, uint64_t* out_dev, const uint64_t* shares_dev,
                              size_t share_stride, size_t n, size_t N, void* stream);
 
 /* ---- matrices: scl::math::Matrix ------------------------------------------ */
 /* Matrix::vandermonde(n, m, xs) (matrix.h:444-460), row-major into V_dev; xs NULL = 1..n */
+/* Aliasing: V_dev is the only device operand. */
 int scl_hip_vandermonde(int field, uint64_t* V_dev, size_t n, size_t m, const uint64_t* xs_host,
                         void* stream);
 /* Matrix::multiply (matrix.h:477-495): C[M x N] = A[M x K] * B[K x N], all row-major, with
  * leading dimensions lda/ldb/ldc in elements. */
+/* Aliasing: C_dev must not overlap any other operand (C on B is right or wrong by the kernel the shape selects: refused for
+ * every shape). */
 int scl_hip_matmul(int field, uint64_t* C_dev, size_t ldc, const uint64_t* A_dev, size_t lda,
                    const uint64_t* B_dev, size_t ldb, size_t M, size_t K, size_t N, void* stream);
 
 /* ---- layout ---------------------------------------------------------------- */
 /* AoS [N][n] (one reference Vector per secret) <-> SoA [n][stride] */
+/* Aliasing: soa_dev must not overlap aos_dev. */
 int scl_hip_aos_to_soa(int field, uint64_t* soa_dev, size_t stride, const uint64_t* aos_dev,
                        size_t N, size_t n, void* stream);
+/* Aliasing: aos_dev must not overlap soa_dev. */
 int scl_hip_soa_to_aos(int field, uint64_t* aos_dev, const uint64_t* soa_dev, size_t stride,
                        size_t N, size_t n, void* stream);
 
@@ -293,9 +331,12 @@ int scl_hip_soa_to_aos(int field, uint64_t* aos_dev, const uint64_t* soa_dev, si
  * include/scl/math/ff.h:355-391, vector.h:595-629): u32 count (little-endian) followed by count
  * elements as FF::write emits them.  Buffers must be 4-byte aligned. */
 size_t scl_hip_wire_size(int field, size_t n); /* 4 + n * byteSize */
+/* Aliasing: dst_dev must not overlap src_dev. */
 int scl_hip_wire_pack(int field, unsigned char* dst_dev, const uint64_t* src_dev, size_t n, void* stream);
 /* Reads the count (synchronous), checks it against nbytes and capacity, then FF::read per element.
  * *n_host receives the element count. */
+/* Aliasing: dst_dev must not overlap src_dev (judged on the whole destination, capacity elements, and all nbytes of the
+ * image, before the count is read). */
 int scl_hip_wire_unpack(int field, uint64_t* dst_dev, size_t capacity, const unsigned char* src_dev,
                         size_t nbytes, size_t* n_host, void* stream);
 
@@ -304,8 +345,11 @@ int scl_hip_wire_unpack(int field, uint64_t* dst_dev, size_t capacity, const uns
  * elements.  unpack reads the 12-byte header synchronously; an image whose count differs from rows*cols is
  * refused (the reference does not check, matrix.h:420). */
 size_t scl_hip_wire_size_matrix(int field, size_t rows, size_t cols); /* 12 + rows * cols * byteSize */
+/* Aliasing: dst_dev must not overlap src_dev. */
 int scl_hip_wire_pack_matrix(int field, unsigned char* dst_dev, const uint64_t* src_dev, size_t ld, size_t rows,
                              size_t cols, void* stream);
+/* Aliasing: dst_dev must not overlap src_dev (judged on capacity_rows rows of ld elements and all nbytes of the image,
+ * before the header is read). */
 int scl_hip_wire_unpack_matrix(int field, uint64_t* dst_dev, size_t ld, size_t capacity_rows,
                                const unsigned char* src_dev, size_t nbytes, size_t* rows_host, size_t* cols_host,
                                void* stream);
@@ -316,14 +360,18 @@ int scl_hip_wire_unpack_matrix(int field, uint64_t* dst_dev, size_t ld, size_t c
  * `packet.read<Vector>()` would: it looks at exactly packet-size bytes.  (A Matrix frame is its 4-byte size in
  * front of scl_hip_wire_unpack_matrix's input.) */
 size_t scl_hip_frame_size(size_t image_bytes);
+/* Aliasing: dst_dev must not overlap src_dev. */
 int scl_hip_frame_pack(int field, unsigned char* dst_dev, const uint64_t* src_dev, size_t n, void* stream);
+/* Aliasing: dst_dev must not overlap src_dev. */
 int scl_hip_frame_pack_matrix(int field, unsigned char* dst_dev, const uint64_t* src_dev, size_t ld, size_t rows,
                               size_t cols, void* stream);
+/* Aliasing: dst_dev must not overlap src_dev (judged as for scl_hip_wire_unpack). */
 int scl_hip_frame_unpack(int field, uint64_t* dst_dev, size_t capacity, const unsigned char* src_dev, size_t nbytes,
                          size_t* n_host, void* stream);
 
 /* ---- roofline probe -------------------------------------------------------- */
 /* plain device copy kernel (16 B per lane) used to measure achievable HBM bandwidth */
+/* Aliasing: dst_dev must not overlap src_dev. */
 int scl_hip_stream_copy(void* dst_dev, const void* src_dev, size_t bytes, void* stream);
 
 /* ---- commitments: scl::util::Sha256 and scl::util::MerkleTree<Sha256, LEAF> ------------------------------------
@@ -335,6 +383,7 @@ int scl_hip_stream_copy(void* dst_dev, const void* src_dev, size_t bytes, void* 
  * Batched Sha256{}.update(msg, msg_len).finalize() (include/scl/util/sha256.h:33-67, iuf_hash.h:41-105,
  * src/scl/util/sha256.cc): message i is the msg_len bytes at msgs_dev + i * msg_stride (any length, any alignment;
  * msg_stride >= msg_len), digest i goes to digests_dev + i * 32. */
+/* Aliasing: digests_dev must not overlap msgs_dev. */
 int scl_hip_sha256(unsigned char* digests_dev, const unsigned char* msgs_dev, size_t msg_len, size_t msg_stride,
                    size_t count, void* stream);
 /* MerkleTree::hashLeafs without its padding (include/scl/util/merkle.h:74-92): digest = Sha256 of the element's
@@ -342,6 +391,7 @@ int scl_hip_sha256(unsigned char* digests_dev, const unsigned char* msgs_dev, si
  * rows x cols window of elements with a row pitch of `stride` elements; the digest of element (row, col) goes to
  * digests_dev + (row * cols + col) * 32.  A share matrix [party][secret] passed whole (rows = n, cols = N) is therefore the
  * leaf level of N trees of n leaves in the layout below.  Ring tags are refused (no Serializer<Z2k> in the reference). */
+/* Aliasing: digests_dev must not overlap a_dev. */
 int scl_hip_merkle_leaves(int field, unsigned char* digests_dev, const uint64_t* a_dev, size_t stride, size_t rows,
                           size_t cols, void* stream);
 /* The shape of the reference's tree over L leaves (merkle.h:85-89,110-116: the leaf level and every later level of odd size
@@ -356,9 +406,11 @@ size_t scl_hip_merkle_tree_bytes(size_t L, size_t T);
  * level_offset(l + 1) = level_offset(l) + level_size(L, l) * T * 32; the T roots are the last T * 32 bytes.
  * leaf_digests_dev holds level 0 in the same layout and is copied in; it may BE tree_dev (no copy), not overlap otherwise.
  * L = 0 or T = 0: SCL_ERR_BAD_ARG (the reference reads digests[0] of an empty vector). */
+/* Aliasing: tree_dev may be leaf_digests_dev (no copy then). */
 int scl_hip_merkle_build(unsigned char* tree_dev, const unsigned char* leaf_digests_dev, size_t L, size_t T, void* stream);
 /* The same reduction keeping nothing but the roots: roots_dev[tau * 32 ..]; the levels in between live in the calling
  * thread's temporary arena (two levels' worth: 24 * T * L bytes at most). */
+/* Aliasing: roots_dev must not overlap leaf_digests_dev. */
 int scl_hip_merkle_root(unsigned char* roots_dev, const unsigned char* leaf_digests_dev, size_t L, size_t T, void* stream);
 /* MerkleTree::prove (merkle.h:122-162) for k queries against a built batch: path_dev[(l * k + q) * 32 ..] = the sibling
  * of query q's node at level l < depth (the node itself where the reference repeats it).  Query q asks for leaf
@@ -369,6 +421,7 @@ int scl_hip_merkle_root(unsigned char* roots_dev, const unsigned char* leaf_dige
  * leaf_index_dev is given; a regular pattern that reaches a leaf >= L is SCL_ERR_INVALID_RANGE.  The reference's
  * direction[l] is bit l of the leaf index (merkle.h:140-148), so its Bitmap is the index's low `depth` bits, little-endian
  * bytes (bitmap.h:88-103): the index is the proof's second half and is not written here. */
+/* Aliasing: path_dev must not overlap any other operand. */
 int scl_hip_merkle_paths(unsigned char* path_dev, const unsigned char* tree_dev, size_t L, size_t T,
                          const uint64_t* leaf_index_dev, const uint64_t* tree_index_dev, size_t first_leaf, size_t k,
                          void* stream);
@@ -378,6 +431,7 @@ int scl_hip_merkle_paths(unsigned char* path_dev, const unsigned char* tree_dev,
  * or root q mod num_roots when that is NULL.  A device index out of range (leaf >= 2^depth, root >= num_roots) is
  * masked / clamped and the query's byte is 0; `leaf` >= 2^depth from the host is SCL_ERR_INVALID_RANGE.  Never faults on a
  * bad proof, and no lane leaves early on its data. */
+/* Aliasing: ok_dev must not overlap any other operand. */
 int scl_hip_merkle_verify(unsigned char* ok_dev, const unsigned char* leaf_digests_dev, const uint64_t* leaf_index_dev,
                           size_t leaf, const unsigned char* path_dev, size_t depth, const unsigned char* roots_dev,
                           const uint64_t* root_index_dev, size_t num_roots, size_t k, void* stream);
@@ -400,55 +454,66 @@ int scl_hip_merkle_verify(unsigned char* ok_dev, const unsigned char* leaf_diges
 int scl_hip_ec_generator(uint64_t point_host[12]);
 /* Vector<EC> element-wise (vector.h add / subtract over EC: secp256k1_curve.cc:119-230, 276-290): op = SCL_OP_ADD, SCL_OP_SUB,
  * SCL_OP_NEG (b_dev ignored) or SCL_EC_OP_DBL (b_dev ignored).  dst_dev may be a_dev or b_dev. */
+/* Aliasing: dst_dev may be a_dev; dst_dev may be b_dev (and a_dev may be b_dev: two inputs; all three may be one buffer). */
 int scl_hip_ec_ew(int op, uint64_t* dst_dev, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, void* stream);
 /* EC::operator== per pair (secp256k1_curve.cc:77-84, cross-multiplication): eq_dev[i] = 1 or 0. */
+/* Aliasing: eq_dev must not overlap any other operand. */
 int scl_hip_ec_equal(unsigned char* eq_dev, const uint64_t* a_dev, const uint64_t* b_dev, size_t n, void* stream);
 /* The window table of a base point B for scl_hip_ec_mul_base: 64 windows of 4 bits, each the affine multiples 1..15 of
  * 16^w * B.  The caller owns the buffer of scl_hip_ec_base_table_bytes() bytes (device memory, 16-byte aligned); it is written
  * once by this call and only read afterwards.  base_host is read before the call returns.  B = infinity: SCL_ERR_BAD_ARG. */
 size_t scl_hip_ec_base_table_bytes(void);
+/* Aliasing: table_dev is the only device operand. */
 int scl_hip_ec_base_table(void* table_dev, const uint64_t base_host[12], void* stream);
 /* dst_dev[i] = scalars_dev[i] * B (EC::operator*(FF<Scalar>), secp256k1_curve.cc:309-326) from B's table. */
+/* Aliasing: dst_dev must not overlap any other operand. */
 int scl_hip_ec_mul_base(uint64_t* dst_dev, const void* table_dev, const uint64_t* scalars_dev, size_t n, void* stream);
 /* dst_dev[i] = sum over k < m of scalars_dev[k] * points_dev[k * row_stride + i], i < n: m rows of n points and ONE scalar per
- * row, read from device memory -- the sum of feldmanVerify (feldman.h:150-156).  m >= 1; dst_dev must not overlap points_dev. */
+ * row, read from device memory -- the sum of feldmanVerify (feldman.h:150-156).  m >= 1. */
+/* Aliasing: dst_dev must not overlap any other operand. */
 int scl_hip_ec_lincomb(uint64_t* dst_dev, const uint64_t* points_dev, size_t row_stride, size_t m,
                        const uint64_t* scalars_dev, size_t n, void* stream);
 /* Serializer<EC>::write / read (ec.h:315-339; secp256k1_curve.cc:357-431), always uncompressed: image i is the 65 bytes at
  * i * 65 -- 0x04, x, y (affine, big-endian, out of Montgomery form), or 0x06 and 64 zero bytes for infinity.  Reading: the
  * infinity flag (0x02) wins and the rest is ignored; a full point is not checked to lie on the curve; status_dev[i] = 0, or 1
  * for an image with neither flag (a compressed point: not supported, the point written is infinity). */
+/* Aliasing: dst_dev must not overlap points_dev. */
 int scl_hip_ec_wire_pack(unsigned char* dst_dev, const uint64_t* points_dev, size_t n, void* stream);
+/* Aliasing: points_dev must not overlap any other operand; status_dev must not overlap any other operand. */
 int scl_hip_ec_wire_unpack(uint64_t* points_dev, unsigned char* status_dev, const unsigned char* src_dev, size_t n,
                            void* stream);
 /* The commitments of feldmanSecretShare (feldman.h:107-127) for N secrets: commit_dev[k * commit_stride + s] = f_s(k) * G,
  * k = 0..t -- row 0 from secrets_dev[s], row k from share row k - 1 (shares_dev[(k - 1) * share_stride + s], the SoA share
  * matrix of scl_hip_shamir_share*).  gtable_dev is the table of the generator. */
+/* Aliasing: commit_dev must not overlap any other operand. */
 int scl_hip_feldman_commit(uint64_t* commit_dev, size_t commit_stride, const void* gtable_dev, const uint64_t* secrets_dev,
                            const uint64_t* shares_dev, size_t share_stride, size_t t, size_t N, void* stream);
 /* feldmanVerify (feldman.h:140-163) for N secrets at one index: ok_dev[s] = 1 iff sum_k lambda_k * commit[k][s] ==
  * share_dev[s] * G.  lambda_dev: the t + 1 scalars of scl_hip_lagrange_basis(SCL_SECP256K1_SCALAR) over the nodes 0..t at
  * the index, copied to the device by the caller (party p, 0-based, verifies at index p + 1; index 0 verifies the secret).
  * scratch_points_dev: 2 N points owned by the caller. */
+/* Aliasing: ok_dev must not overlap any other operand; scratch_points_dev must not overlap any other operand. */
 int scl_hip_feldman_verify(unsigned char* ok_dev, const uint64_t* share_dev, const uint64_t* commit_dev, size_t commit_stride,
                            size_t t, const uint64_t* lambda_dev, const void* gtable_dev, uint64_t* scratch_points_dev,
                            size_t N, void* stream);
 
 /* dst_dev[i] = a_dev[i] * G + b_dev[i] * H from the window tables of G and H (the commitment of pedersen.h:143,145 and the
  * right-hand side of pedersenVerify, pedersen.h:206): one accumulator, 128 mixed additions, no doubling. */
+/* Aliasing: dst_dev must not overlap any other operand. */
 int scl_hip_ec_mul_two_base(uint64_t* dst_dev, const void* gtable_dev, const void* htable_dev, const uint64_t* a_dev,
                             const uint64_t* b_dev, size_t n, void* stream);
 /* The point side of ss::apply (pedersen.h:262-271): dst_dev[i * dst_stride + c] = sum over k < p of M_dev[i * p + k] *
  * points_dev[k * row_stride + c], i < rows, c < cols -- a rows x p matrix of scalars (row-major, device memory) times a p x cols
  * matrix of points.  The doubling chain of output row i starts at the highest bit set in row i of M, so a matrix of small
- * entries (identity, Vandermonde) costs in proportion to its bit length; a row of zeros gives infinity.  p >= 1;
- * dst_dev must not overlap points_dev (SCL_ERR_BAD_ARG). */
+ * entries (identity, Vandermonde) costs in proportion to its bit length; a row of zeros gives infinity.  p >= 1. */
+/* Aliasing: dst_dev must not overlap any other operand. */
 int scl_hip_ec_matmul(uint64_t* dst_dev, size_t dst_stride, const uint64_t* M_dev, size_t rows, size_t p,
                       const uint64_t* points_dev, size_t row_stride, size_t cols, void* stream);
 /* The commitments of pedersenSecretShare (pedersen.h:140-146) for N secrets over the packed layout of
  * scl_hip_shamir_share_prg_packed with width = 2: component j of the secret at secrets_dev + j * secret_stride, component j of
  * party i at shares_dev + (j * n + i) * share_stride (strides in elements).  commit_dev[0 * commit_stride + s] = secret_s * G +
  * blinding_s * H, row k = 1..t from party k - 1.  n < t: SCL_ERR_SIZE_MISMATCH.  htable_dev is the table of H. */
+/* Aliasing: commit_dev must not overlap any other operand (of shares_dev, rows 0 .. n+t-1 count). */
 int scl_hip_pedersen_commit(uint64_t* commit_dev, size_t commit_stride, const void* gtable_dev, const void* htable_dev,
                             const uint64_t* secrets_dev, size_t secret_stride, const uint64_t* shares_dev, size_t share_stride,
                             size_t t, size_t n, size_t N, void* stream);
@@ -456,6 +521,7 @@ int scl_hip_pedersen_commit(uint64_t* commit_dev, size_t commit_stride, const vo
  * share_dev[s] * G + rand_dev[s] * H.  lambda_dev as for scl_hip_feldman_verify: the basis over the nodes 0..t at the index; the
  * reference's shortcut for an index <= t (pedersen.h:181-183) is the unit-vector case of the same sum.  scratch_points_dev: 2 N
  * points owned by the caller. */
+/* Aliasing: ok_dev must not overlap any other operand; scratch_points_dev must not overlap any other operand. */
 int scl_hip_pedersen_verify(unsigned char* ok_dev, const uint64_t* share_dev, const uint64_t* rand_dev, const uint64_t* commit_dev,
                             size_t commit_stride, size_t t, const uint64_t* lambda_dev, const void* gtable_dev,
                             const void* htable_dev, uint64_t* scratch_points_dev, size_t N, void* stream);
@@ -473,27 +539,33 @@ int scl_hip_pedersen_verify(unsigned char* ok_dev, const uint64_t* share_dev, co
  *
  * dst_dev[i] = scalars_dev[i] * points_dev[i] (EC::operator*(FF<Scalar>) over a vector, secp256k1_curve.cc:309-326): a point
  * and a scalar per lane, 4-bit windows over a table of the lane's own in scratch_dev -- scl_hip_ec_mul_scratch_bytes(n) bytes
- * of device memory, 16-byte aligned, owned by the caller, contents meaningless between calls.  dst_dev may be points_dev. */
+ * of device memory, 16-byte aligned, owned by the caller, contents meaningless between calls. */
 size_t scl_hip_ec_mul_scratch_bytes(size_t n);
+/* Aliasing: dst_dev may be points_dev (the lane's table is built before its point is overwritten); dst_dev must not overlap
+ * scalars_dev; scratch_dev must not overlap any other operand. */
 int scl_hip_ec_mul(uint64_t* dst_dev, const uint64_t* points_dev, const uint64_t* scalars_dev, void* scratch_dev, size_t n,
                    void* stream);
 /* ECDSA::conversionFunc (sign.h:157-162) per point: the affine x as an integer, mod the group order; infinity gives 0. */
+/* Aliasing: scalars_dev must not overlap points_dev. */
 int scl_hip_ecdsa_conversion(uint64_t* scalars_dev, const uint64_t* points_dev, size_t n, void* stream);
 /* ECDSA::Sign (sign.h:116-126) with the nonces supplied: sig_dev[i] = (r, s), r = conversionFunc(nonces_dev[i] * G),
  * s = nonces_dev[i]^-1 * (h_i + sk * r).  The library draws no nonce: the caller fills nonces_dev (the reference draws
  * SecretKey::random(prg) per signature).  A zero nonce, where the reference's inverse throws (ff_ops_gmp.h:250-260), writes
  * (0, 0) and sets *status_dev (one 32-bit device word, never cleared by the call, may be NULL) to 1; r == 0 or s == 0 for any
  * other reason is not checked, as in the reference.  gtable_dev is the table of the generator. */
+/* Aliasing: sig_dev must not overlap any other operand; status_dev must not overlap any other operand. */
 int scl_hip_ecdsa_sign(uint64_t* sig_dev, const void* gtable_dev, const uint64_t* sk_dev, size_t sk_stride,
                        const uint64_t* nonces_dev, const unsigned char* digests_dev, unsigned* status_dev, size_t n, void* stream);
 /* ECDSA::verify (sign.h:135-146) per signature: verdict_dev[i] = 1 accepted, 0 rejected, 2 where s == 0 (the reference's
  * s.inverse() throws there).  Every lane inverts its own s, so a zero has no effect on its neighbours.  scratch_dev as for
  * scl_hip_ec_mul.  Public keys are not checked to lie on the curve. */
+/* Aliasing: verdict_dev must not overlap any other operand; scratch_dev must not overlap any other operand. */
 int scl_hip_ecdsa_verify(unsigned char* verdict_dev, const uint64_t* sig_dev, const unsigned char* digests_dev,
                          const uint64_t* pk_dev, size_t pk_stride, const void* gtable_dev, void* scratch_dev, size_t n,
                          void* stream);
 /* The same verdicts when every signature is ONE signer's: qtable_dev is the window table of the public key
  * (scl_hip_ec_base_table), and no scratch is needed. */
+/* Aliasing: verdict_dev must not overlap any other operand. */
 int scl_hip_ecdsa_verify_base(unsigned char* verdict_dev, const uint64_t* sig_dev, const unsigned char* digests_dev,
                               const void* qtable_dev, const void* gtable_dev, size_t n, void* stream);
 

@@ -23,6 +23,7 @@
 #endif
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/field.hpp"
+#include "../../include/scl_hip/detail/span.hpp"
 #include "kernels.hpp"
 #include "share_mfma.hpp"
 
@@ -512,6 +513,15 @@ int check_align(std::initializer_list<const void*> ptrs) {
   for (const void* p : ptrs)
     if (p && (reinterpret_cast<uintptr_t>(p) & mask))
       return fail(SCL_ERR_BAD_ARG, F::LIMBS == 1 ? "pointer not 8-byte aligned" : "pointer not 16-byte aligned");
+  return SCL_OK;
+}
+
+// The aliasing rule of scl_hip.h (Conventions): the call's device operands as bounding spans (detail/span.hpp); an overlap the
+// entry point does not permit is refused here, before anything is enqueued.
+using alias::Operand;
+int alias_check(const char* who, std::initializer_list<Operand> ops) {
+  std::string msg;
+  if (alias::conflict(who, ops.begin(), ops.size(), &msg) != alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
   return SCL_OK;
 }
 
@@ -1453,6 +1463,10 @@ static int ew_impl(int field, int op, uint64_t* dst, const uint64_t* a, const ui
   return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({dst, a, binary ? b : nullptr}));
+    SCL_TRY(alias_check(async ? "ew_status" : "ew",
+                        {alias::vec("dst_dev", dst, n, F::LIMBS * 8, true, 1), alias::vec("a_dev", a, n, F::LIMBS * 8, false, 1),
+                         alias::vec("b_dev", binary ? b : nullptr, n, F::LIMBS * 8, false, 1),
+                         alias::vec("status_dev", async ? status_dev : nullptr, 1, 4, true)}));
     unsigned* flag = nullptr;
     bool host_flag = false;
     if (needs_flag && async) {
@@ -1549,6 +1563,7 @@ int scl_hip_scalar_mul(int field, uint64_t* dst, const uint64_t* a, const uint64
   return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({dst, a}));
+    SCL_TRY(alias_check("scalar_mul", {alias::vec("dst_dev", dst, n, F::LIMBS * 8, true, 1), alias::vec("a_dev", a, n, F::LIMBS * 8, false, 1)}));
     Table<F> sc;
     sc.v[0] = F::ld(scalar_host);
     const int vec = vec_width<F>({dst, a}, {});
@@ -1713,6 +1728,15 @@ static int ring_from_bytes(int field, uint64_t* dst, const unsigned char* src, s
 int scl_hip_from_bytes(int field, uint64_t* dst, const unsigned char* src, size_t n, void* stream) {
   if (n == 0) return SCL_OK;
   if (!dst || !src) return fail(SCL_ERR_BAD_ARG, "NULL operand");
+  {
+    const int L = scl_hip_limbs(field);
+    if (L < 0) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+    const size_t bs = is_ring(field) ? (size_t)(field - 0x100 - 1) / 8 + 1 : (size_t)L * 8;  // FF::byteSize / Z2k::byteSize
+    // in place (the open step folds its reduce-scatter slice this way) where element q's bytes are element q's words: every field,
+    // and a ring whose byteSize fills its limbs; a narrower ring packs its bytes tighter than its elements and is refused
+    const int same = bs == (size_t)L * 8 ? 1 : 0;
+    SCL_TRY(alias_check("from_bytes", {alias::vec("dst_dev", dst, n, (size_t)L * 8, true, same), alias::vec("src_dev", src, n, bs, false, same)}));
+  }
   if (is_ring(field)) return ring_from_bytes(field, dst, src, n, S(stream));
   return with_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
@@ -1782,6 +1806,8 @@ int scl_hip_shamir_recover(int field, uint64_t* out, const uint64_t* shares, siz
   if (stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "share_stride < N");
   const int L = scl_hip_limbs(field);
   if (L < 0 || is_ring(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+  SCL_TRY(alias_check("shamir_recover", {alias::vec("out_dev", out, N, (size_t)L * 8, true),
+                                         alias::mat("shares_dev", shares, m, stride, N, (size_t)L * 8, false)}));
   // shamirRecoverP takes any number of shares (shamir.h:81-87); one launch holds 256 / limbs Lagrange coefficients.
   // More parties are summed over several launches, each adding its block's terms to the canonical partial sum.
   const size_t cap = (size_t)256 / (size_t)L;
@@ -1886,6 +1912,9 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
     // block by block (parties are independent).  More than 48 coefficients go through the chunked Horner kernel.
     const int L = scl_hip_limbs(field);
     if (L < 0 || is_ring(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+    SCL_TRY(alias_check("shamir_share", {alias::mat("shares_dev", shares, n, share_stride, N, (size_t)L * 8, true),
+                                         alias::vec("secrets_dev", secrets, N, (size_t)L * 8, false),
+                                         alias::mat("coeffs_dev", coeffs, t, coeff_stride, N, (size_t)L * 8, false)}));
     const size_t cap = (size_t)256 / (size_t)L;
     if (n > cap) {
       std::vector<u64> nodes(n * (size_t)L);
@@ -2138,6 +2167,9 @@ int scl_hip_shamir_share_prg_packed(int field, uint64_t* shares, size_t share_st
   if (secret_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "stride < N");
   const int L = scl_hip_limbs(field);
   if (L < 0) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+  if (share_stride >= N)  // (a shorter stride is refused below)
+    SCL_TRY(alias_check("shamir_share_prg_packed", {alias::mat("shares_dev", shares, width * n, share_stride, N, (size_t)L * 8, true),
+                                                    alias::mat("secrets_dev", secrets, width, secret_stride, N, (size_t)L * 8, false)}));
   for (size_t j = 0; j < width; ++j)
     SCL_TRY(share_prg_impl(field, shares + j * n * share_stride * (size_t)L, share_stride,
                            secrets + j * secret_stride * (size_t)L, N, t, n, seed, seed_len, counter0,
@@ -2154,6 +2186,8 @@ static int share_prg_impl(int field, uint64_t* shares, size_t share_stride, cons
   {
     const int L = scl_hip_limbs(field);
     if (L < 0 || is_ring(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
+    SCL_TRY(alias_check("shamir_share_prg", {alias::mat("shares_dev", shares, n, share_stride, N, (size_t)L * 8, true),
+                                             alias::vec("secrets_dev", secrets, N, (size_t)L * 8, false)}));
     const size_t cap = (size_t)256 / (size_t)L;
     // One fused kernel (coefficients drawn into registers, evaluated in place) or two passes (rows drawn into a temporary,
     // then the explicit-coefficient kernel of the shape).  Fused wins where its kernel is small and the evaluation cheap: the
@@ -2288,6 +2322,8 @@ int scl_hip_shamir_recover_detect(int field, uint64_t* out, unsigned char* statu
   return with_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({out, shares}));
+    SCL_TRY(alias_check("shamir_recover_detect", {alias::vec("out_dev", out, N, F::LIMBS * 8, true), alias::vec("status_dev", status, N, 1, true),
+                                                  alias::mat("shares_dev", shares, m, stride, N, F::LIMBS * 8, false)}));
     std::vector<typename F::E> alphas;
     if (alphas_host) load_host<F>(alphas_host, m, alphas);
     else default_nodes<F>(ctx, m, alphas);
@@ -2384,6 +2420,10 @@ int scl_hip_shamir_recover_correct(int field, uint64_t* f_out, size_t f_stride, 
     using F = decltype(f);
     typedef typename F::E E;
     SCL_TRY(check_align<F>({f_out, e_out, shares}));
+    SCL_TRY(alias_check("shamir_recover_correct",
+                        {alias::mat("f_dev", f_out, n, f_stride, N, F::LIMBS * 8, true), alias::mat("e_dev", e_out, t + 1, e_stride, N, F::LIMBS * 8, true),
+                         alias::vec("status_dev", status, N, 1, true), alias::vec("nerr_dev", nerr, N, 4, true),
+                         alias::mat("shares_dev", shares, m, stride, N, F::LIMBS * 8, false)}));
     std::vector<E> alphas;
     if (alphas_host) load_host<F>(alphas_host, n, alphas);
     else default_nodes<F>(ctx, n, alphas);
@@ -2496,6 +2536,10 @@ int scl_hip_additive_share(int field, uint64_t* shares, size_t share_stride, con
   return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({shares, secrets, rnd}));
+    // (rnd == shares at one stride: a lane stores back the very elements it loaded, then its own column of the last row)
+    SCL_TRY(alias_check("additive_share", {alias::mat("shares_dev", shares, n, share_stride, N, F::LIMBS * 8, true, 1),
+                                           alias::vec("secrets_dev", secrets, N, F::LIMBS * 8, false),
+                                           alias::mat("rnd_dev", n > 1 ? rnd : nullptr, n - 1, rnd_stride, N, F::LIMBS * 8, false, 1)}));
     const int vec = vec_width<F>({shares, secrets, rnd}, {share_stride, n > 1 ? rnd_stride : 0});
     return split_vec<F>(vec, N, [&](auto V, size_t first, size_t npacks) -> int {
       constexpr int VEC = decltype(V)::value;
@@ -2518,6 +2562,8 @@ int scl_hip_additive_share_prg(int field, uint64_t* shares, size_t share_stride,
   return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({shares, secrets}));
+    SCL_TRY(alias_check("additive_share_prg", {alias::mat("shares_dev", shares, n, share_stride, N, F::LIMBS * 8, true),
+                                               alias::vec("secrets_dev", secrets, N, F::LIMBS * 8, false)}));
     AesKey key;
     make_aes_key(seed, seed_len, key);
     aes_key_range(key, (u64)counter0, (u64)N * (n - 1) * ((F::LIMBS * 8 + 15) / 16));
@@ -2541,6 +2587,8 @@ int scl_hip_additive_recover(int field, uint64_t* out, const uint64_t* shares, s
   return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({out, shares}));
+    SCL_TRY(alias_check("additive_recover", {alias::vec("out_dev", out, N, F::LIMBS * 8, true),
+                                             alias::mat("shares_dev", shares, n, stride, N, F::LIMBS * 8, false)}));
     const int vec = vec_width<F>({out, shares}, {stride});
     return split_vec<F>(vec, N, [&](auto V, size_t first, size_t npacks) -> int {
       constexpr int VEC = decltype(V)::value;
@@ -2594,6 +2642,9 @@ int scl_hip_matmul(int field, uint64_t* C, size_t ldc, const uint64_t* A, size_t
   return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({C, A, B}));
+    // (C on B is right on k_matmul_thin and wrong on k_matmul -- docs/kernels/r1_r4_matrix_layout_wire.md -- so no path takes it)
+    SCL_TRY(alias_check("matmul", {alias::mat("C_dev", C, M, ldc, N, F::LIMBS * 8, true), alias::mat("A_dev", K ? A : nullptr, M, lda, K, F::LIMBS * 8, false),
+                                   alias::mat("B_dev", K ? B : nullptr, K, ldb, N, F::LIMBS * 8, false)}));
     if (K == 0) {  // an empty sum: the zero matrix
       for (size_t i = 0; i < M; ++i) HIP_TRY(hipMemsetAsync(C + i * ldc * F::LIMBS, 0, N * F::LIMBS * 8, S(stream)));
       return SCL_OK;
@@ -2693,6 +2744,10 @@ static int transpose_impl(int field, uint64_t* dst, const uint64_t* src, size_t 
   if (N == 0 || n == 0) return SCL_OK;
   if (!dst || !src) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "stride < N");
+  if (to_soa)
+    SCL_TRY(alias_check("aos_to_soa", {alias::mat("soa_dev", dst, n, stride, N, (size_t)L * 8, true), alias::mat("aos_dev", src, N, n, n, (size_t)L * 8, false)}));
+  else
+    SCL_TRY(alias_check("soa_to_aos", {alias::mat("aos_dev", dst, N, n, n, (size_t)L * 8, true), alias::mat("soa_dev", src, n, stride, N, (size_t)L * 8, false)}));
   // 16-byte accesses on both sides (k_transpose16) where the layout allows: aligned bases, an even row stride for one-limb
   // fields, and a tile of at least 64 secrets within 40 KiB of LDS ("force_scalar" 1: the 8-byte kernel, for A/B runs)
   {
@@ -2782,6 +2837,8 @@ static int wire_pack_impl(int field, unsigned char* dst, const uint64_t* src, si
   return with_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({src}));
+    SCL_TRY(alias_check(framed ? "frame_pack" : "wire_pack", {alias::vec("dst_dev", dst, (framed ? 8 : 4) + n * F::LIMBS * 8, 1, true),
+                                                              alias::vec("src_dev", src, n, F::LIMBS * 8, false)}));
     // framed: TcpChannel::send's u32 packet size in front (tcp_channel.h:127-137)
     const u32 image = (u32)(4 + n * F::LIMBS * 8);
     const WireGeom g = framed ? WireGeom{{image, (u32)n, 0, 0}, 2, n, n} : WireGeom{{(u32)n, 0, 0, 0}, 1, n, n};
@@ -2821,6 +2878,9 @@ static int wire_pack_matrix_impl(int field, unsigned char* dst, const uint64_t* 
   return with_field(field, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     SCL_TRY(check_align<F>({src}));
+    SCL_TRY(alias_check(framed ? "frame_pack_matrix" : "wire_pack_matrix",
+                        {alias::vec("dst_dev", dst, (framed ? 16 : 12) + n * F::LIMBS * 8, 1, true),
+                         alias::mat("src_dev", n ? src : nullptr, rows, ld, cols, F::LIMBS * 8, false)}));
     const u32 image = (u32)(12 + n * F::LIMBS * 8);
     if (framed && 12 + n * F::LIMBS * 8 > 0xFFFFFFFFull) return fail(SCL_ERR_BAD_ARG, "frame larger than the u32 packet size");
     const WireGeom g = framed ? WireGeom{{image, (u32)rows, (u32)cols, (u32)n}, 4, cols ? cols : 1, n ? ld : 1}
@@ -2837,6 +2897,9 @@ int scl_hip_wire_unpack_matrix(int field, uint64_t* dst, size_t ld, size_t capac
   if (!src || !rows_host || !cols_host) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (reinterpret_cast<uintptr_t>(src) & 3) return fail(SCL_ERR_BAD_ARG, "wire buffer not 4-byte aligned");
   if (nbytes < 12) return fail(SCL_ERR_BAD_ARG, "wire image shorter than its header");
+  if (const int L0 = scl_hip_limbs(field); L0 > 0)  // the whole destination, capacity_rows rows of ld, against the whole image
+    SCL_TRY(alias_check("wire_unpack_matrix", {alias::mat("dst_dev", dst, capacity_rows, ld, ld, (size_t)L0 * 8, true),
+                                               alias::vec("src_dev", src, nbytes, 1, false)}));
   u32 hdr[3] = {0, 0, 0};
   HIP_TRY(hipMemcpyAsync(hdr, src, 12, hipMemcpyDeviceToHost, S(stream)));
   HIP_TRY(hipStreamSynchronize(S(stream)));
@@ -2879,6 +2942,9 @@ static int wire_unpack_impl(int field, uint64_t* dst, size_t capacity, const uns
   if (reinterpret_cast<uintptr_t>(src) & 3) return fail(SCL_ERR_BAD_ARG, "wire buffer not 4-byte aligned");
   const size_t hdr_bytes = framed ? 8 : 4;
   if (nbytes < hdr_bytes) return fail(SCL_ERR_BAD_ARG, "wire image shorter than its count");
+  if (const int L0 = scl_hip_limbs(field); L0 > 0)  // the whole destination, `capacity` elements, against the whole image
+    SCL_TRY(alias_check(framed ? "frame_unpack" : "wire_unpack", {alias::vec("dst_dev", dst, capacity, (size_t)L0 * 8, true),
+                                                                  alias::vec("src_dev", src, nbytes, 1, false)}));
   u32 head[2] = {0, 0};
   HIP_TRY(hipMemcpyAsync(head, src, hdr_bytes, hipMemcpyDeviceToHost, S(stream)));
   HIP_TRY(hipStreamSynchronize(S(stream)));
@@ -2912,6 +2978,7 @@ int scl_hip_stream_copy(void* dst, const void* src, size_t bytes, void* stream) 
   if (bytes == 0) return SCL_OK;
   if (!dst || !src || !aligned16(dst) || !aligned16(src) || (bytes & 15))
     return fail(SCL_ERR_BAD_ARG, "stream_copy: 16-byte aligned buffers and sizes only");
+  SCL_TRY(alias_check("stream_copy", {alias::vec("dst_dev", dst, bytes, 1, true), alias::vec("src_dev", src, bytes, 1, false)}));
   const size_t n16 = bytes / 16;
   hipLaunchKernelGGL(k_copy16<>, dim3(grid_for(n16)), dim3(BLOCK), 0, S(stream), static_cast<u64x2*>(dst),
                      static_cast<const u64x2*>(src), n16);

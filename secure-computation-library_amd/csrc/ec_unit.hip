@@ -14,6 +14,7 @@
 
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/secp256k1.hpp"
+#include "../../include/scl_hip/detail/span.hpp"
 
 namespace sclhip {
 namespace {
@@ -159,6 +160,14 @@ int fail(int code, const std::string& msg) {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
+constexpr size_t PT_BYTES = POINT_LIMBS * sizeof(uint64_t);
+int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
+  std::string msg;
+  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
+  return SCL_OK;
+}
+
 int mul_base_rows(u64* dst, size_t dst_stride, const void* table, const u64* scalars, size_t src_stride, size_t rows, size_t n,
                   hipStream_t st) {
   if (rows == 0 || n == 0) return SCL_OK;
@@ -195,6 +204,8 @@ int scl_hip_ec_ew(int op, uint64_t* dst, const uint64_t* a, const uint64_t* b, s
   if (n == 0) return SCL_OK;
   if (!dst || !a || (binary && !b)) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(dst) || !aligned16(a) || !aligned16(b)) return fail(SCL_ERR_BAD_ARG, "point buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_ew", {alias::vec("dst_dev", dst, n, PT_BYTES, true, 1), alias::vec("a_dev", a, n, PT_BYTES, false, 1),
+                                alias::vec("b_dev", binary ? b : nullptr, n, PT_BYTES, false, 1)}));
   hipLaunchKernelGGL(k_ec_ew, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), op, dst, a, b, n);
   HIP_TRY(hipGetLastError());
   return SCL_OK;
@@ -204,6 +215,7 @@ int scl_hip_ec_equal(unsigned char* eq, const uint64_t* a, const uint64_t* b, si
   if (n == 0) return SCL_OK;
   if (!eq || !a || !b) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(a) || !aligned16(b)) return fail(SCL_ERR_BAD_ARG, "point buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_equal", {alias::vec("eq_dev", eq, n, 1, true), alias::vec("a_dev", a, n, PT_BYTES, false), alias::vec("b_dev", b, n, PT_BYTES, false)}));
   hipLaunchKernelGGL(k_ec_equal, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), eq, a, b, n);
   HIP_TRY(hipGetLastError());
   return SCL_OK;
@@ -226,6 +238,8 @@ int scl_hip_ec_mul_base(uint64_t* dst, const void* table, const uint64_t* scalar
   if (n == 0) return SCL_OK;
   if (!dst || !table || !scalars) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(dst) || !aligned16(table) || !aligned16(scalars)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_mul_base", {alias::vec("dst_dev", dst, n, PT_BYTES, true), alias::vec("table_dev", table, scl_hip_ec_base_table_bytes(), 1, false),
+                                      alias::vec("scalars_dev", scalars, n, 32, false)}));
   return mul_base_rows(dst, n, table, scalars, n, 1, n, S(stream));
 }
 
@@ -236,6 +250,9 @@ int scl_hip_ec_lincomb(uint64_t* dst, const uint64_t* points, size_t row_stride,
   if (!dst || !points || !scalars) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(dst) || !aligned16(points) || !aligned16(scalars)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (m > 1 && row_stride < n) return fail(SCL_ERR_SIZE_MISMATCH, "row_stride < n");
+  // (m > 256 takes a second launch that adds to dst: a dst on a later row of points is read after it was written)
+  SCL_TRY(alias_check("ec_lincomb", {alias::vec("dst_dev", dst, n, PT_BYTES, true), alias::mat("points_dev", points, m, row_stride, n, PT_BYTES, false),
+                                     alias::vec("scalars_dev", scalars, m, 32, false)}));
   return lincomb_rows(dst, points, row_stride, m, scalars, n, S(stream));
 }
 
@@ -243,6 +260,7 @@ int scl_hip_ec_wire_pack(unsigned char* dst, const uint64_t* points, size_t n, v
   if (n == 0) return SCL_OK;
   if (!dst || !points) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(points)) return fail(SCL_ERR_BAD_ARG, "point buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_wire_pack", {alias::vec("dst_dev", dst, n, WIRE_BYTES, true), alias::vec("points_dev", points, n, PT_BYTES, false)}));
   hipLaunchKernelGGL(k_ec_wire_pack, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), dst, points, n);
   HIP_TRY(hipGetLastError());
   return SCL_OK;
@@ -252,6 +270,8 @@ int scl_hip_ec_wire_unpack(uint64_t* points, unsigned char* status, const unsign
   if (n == 0) return SCL_OK;
   if (!points || !status || !src) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(points)) return fail(SCL_ERR_BAD_ARG, "point buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_wire_unpack", {alias::vec("points_dev", points, n, PT_BYTES, true), alias::vec("status_dev", status, n, 1, true),
+                                         alias::vec("src_dev", src, n, WIRE_BYTES, false)}));
   hipLaunchKernelGGL(k_ec_wire_unpack, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), points, status, src, n);
   HIP_TRY(hipGetLastError());
   return SCL_OK;
@@ -265,6 +285,9 @@ int scl_hip_feldman_commit(uint64_t* commit, size_t commit_stride, const void* g
     return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (t && commit_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "commit_stride < N");
   if (t > 1 && share_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "share_stride < N");
+  SCL_TRY(alias_check("feldman_commit", {alias::mat("commit_dev", commit, t + 1, commit_stride, N, PT_BYTES, true),
+                                         alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                         alias::vec("secrets_dev", secrets, N, 32, false), alias::mat("shares_dev", shares, t, share_stride, N, 32, false)}));
   SCL_TRY(mul_base_rows(commit, commit_stride, gtable, secrets, N, 1, N, S(stream)));
   return mul_base_rows(commit + commit_stride * POINT_LIMBS, commit_stride, gtable, shares, share_stride, t, N, S(stream));
 }
@@ -276,6 +299,11 @@ int scl_hip_feldman_verify(unsigned char* ok, const uint64_t* share, const uint6
   if (!aligned16(share) || !aligned16(commit) || !aligned16(lambda) || !aligned16(gtable) || !aligned16(scratch))
     return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (t && commit_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "commit_stride < N");
+  SCL_TRY(alias_check("feldman_verify", {alias::vec("ok_dev", ok, N, 1, true), alias::vec("share_dev", share, N, 32, false),
+                                         alias::mat("commit_dev", commit, t + 1, commit_stride, N, PT_BYTES, false),
+                                         alias::vec("lambda_dev", lambda, t + 1, 32, false),
+                                         alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                         alias::vec("scratch_points_dev", scratch, 2 * N, PT_BYTES, true)}));
   uint64_t* lhs = scratch;
   uint64_t* rhs = scratch + N * POINT_LIMBS;
   SCL_TRY(lincomb_rows(lhs, commit, commit_stride, t + 1, lambda, N, S(stream)));

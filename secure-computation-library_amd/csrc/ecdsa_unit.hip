@@ -16,6 +16,7 @@
 
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/secp256k1.hpp"
+#include "../../include/scl_hip/detail/span.hpp"
 
 namespace sclhip {
 namespace {
@@ -137,6 +138,19 @@ int fail(int code, const std::string& msg) {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned mul_grid(size_t n) { return (unsigned)(mul_slots(n) / EBLOCK); }
+
+// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
+constexpr size_t PT_BYTES = POINT_LIMBS * sizeof(uint64_t);
+int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
+  std::string msg;
+  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
+  return SCL_OK;
+}
+#define SCL_TRY(expr)            \
+  do {                           \
+    int s_ = (expr);             \
+    if (s_ != SCL_OK) return s_; \
+  } while (0)
 }  // namespace
 
 extern "C" {
@@ -148,6 +162,8 @@ int scl_hip_ec_mul(uint64_t* dst, const uint64_t* points, const uint64_t* scalar
   if (!dst || !points || !scalars || !scratch) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(dst) || !aligned16(points) || !aligned16(scalars) || !aligned16(scratch))
     return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_mul", {alias::vec("dst_dev", dst, n, PT_BYTES, true, 1), alias::vec("points_dev", points, n, PT_BYTES, false, 1),
+                                 alias::vec("scalars_dev", scalars, n, 32, false), alias::vec("scratch_dev", scratch, scl_hip_ec_mul_scratch_bytes(n), 1, true)}));
   hipLaunchKernelGGL(k_ec_mul, dim3(mul_grid(n)), dim3(EBLOCK), 0, S(stream), dst, points, scalars, static_cast<u64*>(scratch), n);
   HIP_TRY(hipGetLastError());
   return SCL_OK;
@@ -157,6 +173,7 @@ int scl_hip_ecdsa_conversion(uint64_t* scalars, const uint64_t* points, size_t n
   if (n == 0) return SCL_OK;
   if (!scalars || !points) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(scalars) || !aligned16(points)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ecdsa_conversion", {alias::vec("scalars_dev", scalars, n, 32, true), alias::vec("points_dev", points, n, PT_BYTES, false)}));
   hipLaunchKernelGGL(k_ecdsa_conversion, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), scalars, points, n);
   HIP_TRY(hipGetLastError());
   return SCL_OK;
@@ -169,6 +186,9 @@ int scl_hip_ecdsa_sign(uint64_t* sig, const void* gtable, const uint64_t* sk, si
   if (!aligned16(sig) || !aligned16(gtable) || !aligned16(sk) || !aligned16(nonces)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (reinterpret_cast<uintptr_t>(status) & 3) return fail(SCL_ERR_BAD_ARG, "status_dev is not 4-byte aligned");
   if (sk_stride > 1) return fail(SCL_ERR_BAD_ARG, "ecdsa_sign: sk_stride is 0 (one key) or 1 (a key per signature)");
+  SCL_TRY(alias_check("ecdsa_sign", {alias::vec("sig_dev", sig, n, 64, true), alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                     alias::vec("sk_dev", sk, sk_stride ? n : 1, 32, false), alias::vec("nonces_dev", nonces, n, 32, false),
+                                     alias::vec("digests_dev", digests, n, 32, false), alias::vec("status_dev", status, 1, 4, true)}));
   hipLaunchKernelGGL(k_ecdsa_sign, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), sig, static_cast<const u64*>(gtable), sk, sk_stride,
                      nonces, digests, status, n);
   HIP_TRY(hipGetLastError());
@@ -181,6 +201,10 @@ int scl_hip_ecdsa_verify(unsigned char* verdict, const uint64_t* sig, const unsi
   if (!verdict || !sig || !digests || !pk || !gtable || !scratch) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(sig) || !aligned16(pk) || !aligned16(gtable) || !aligned16(scratch)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (pk_stride > 1) return fail(SCL_ERR_BAD_ARG, "ecdsa_verify: pk_stride is 0 (one key) or 1 (a key per signature)");
+  SCL_TRY(alias_check("ecdsa_verify", {alias::vec("verdict_dev", verdict, n, 1, true), alias::vec("sig_dev", sig, n, 64, false),
+                                       alias::vec("digests_dev", digests, n, 32, false), alias::vec("pk_dev", pk, pk_stride ? n : 1, PT_BYTES, false),
+                                       alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                       alias::vec("scratch_dev", scratch, scl_hip_ec_mul_scratch_bytes(n), 1, true)}));
   hipLaunchKernelGGL(k_ecdsa_verify, dim3(mul_grid(n)), dim3(EBLOCK), 0, S(stream), verdict, sig, digests, pk, pk_stride,
                      static_cast<const u64*>(gtable), static_cast<u64*>(scratch), n);
   HIP_TRY(hipGetLastError());
@@ -192,6 +216,10 @@ int scl_hip_ecdsa_verify_base(unsigned char* verdict, const uint64_t* sig, const
   if (n == 0) return SCL_OK;
   if (!verdict || !sig || !digests || !qtable || !gtable) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(sig) || !aligned16(qtable) || !aligned16(gtable)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ecdsa_verify_base", {alias::vec("verdict_dev", verdict, n, 1, true), alias::vec("sig_dev", sig, n, 64, false),
+                                            alias::vec("digests_dev", digests, n, 32, false),
+                                            alias::vec("qtable_dev", qtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                            alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false)}));
   hipLaunchKernelGGL(k_ecdsa_verify_base, dim3(ec_grid(n)), dim3(EBLOCK), 0, S(stream), verdict, sig, digests,
                      static_cast<const u64*>(qtable), static_cast<const u64*>(gtable), n);
   HIP_TRY(hipGetLastError());

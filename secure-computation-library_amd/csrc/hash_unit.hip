@@ -13,6 +13,7 @@
 #include <string>
 
 #include "../../include/scl_hip.h"
+#include "../../include/scl_hip/detail/span.hpp"
 #include "sha256.hpp"
 
 namespace sclhip {
@@ -254,6 +255,13 @@ int arena_release(hipStream_t st) {
   return SCL_OK;
 }
 
+// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
+int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
+  std::string msg;
+  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
+  return SCL_OK;
+}
+
 int merkle_shape_check(const char* what, size_t L, size_t T) {
   if (L == 0) return fail(SCL_ERR_BAD_ARG, std::string(what) + ": a tree has at least one leaf");
   if (T == 0) return fail(SCL_ERR_BAD_ARG, std::string(what) + ": no trees");
@@ -270,6 +278,7 @@ int scl_hip_sha256(unsigned char* digests, const unsigned char* msgs, size_t msg
   if (!digests || (msg_len && !msgs)) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(digests)) return fail(SCL_ERR_BAD_ARG, "digest buffer not 16-byte aligned");
   if (count > 1 && msg_stride < msg_len) return fail(SCL_ERR_SIZE_MISMATCH, "msg_stride < msg_len");
+  SCL_TRY(alias_check("sha256", {sclhip::alias::vec("digests_dev", digests, count, 32, true), sclhip::alias::mat("msgs_dev", msgs, count, msg_stride, msg_len, 1, false)}));
   HIP_TRY(hash_launch_sha256(digests, msgs, msg_len, msg_stride, count, S(stream)));
   return SCL_OK;
 }
@@ -286,6 +295,8 @@ int scl_hip_merkle_build(unsigned char* tree, const unsigned char* leaf_digests,
   SCL_TRY(merkle_shape_check("merkle_build", L, T));
   if (!tree || !leaf_digests) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(tree) || !aligned16(leaf_digests)) return fail(SCL_ERR_BAD_ARG, "digest buffer not 16-byte aligned");
+  SCL_TRY(alias_check("merkle_build", {sclhip::alias::vec("tree_dev", tree, scl_hip_merkle_tree_bytes(L, T), 1, true, 1),
+                                       sclhip::alias::vec("leaf_digests_dev", leaf_digests, L * T, 32, false, 1)}));
   if (leaf_digests != tree) HIP_TRY(hipMemcpyAsync(tree, leaf_digests, L * T * 32, hipMemcpyDeviceToDevice, S(stream)));
   unsigned char* in = tree;
   for (size_t count = L;; count = (count + 1) / 2) {
@@ -301,6 +312,7 @@ int scl_hip_merkle_root(unsigned char* roots, const unsigned char* leaf_digests,
   SCL_TRY(merkle_shape_check("merkle_root", L, T));
   if (!roots || !leaf_digests) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(roots) || !aligned16(leaf_digests)) return fail(SCL_ERR_BAD_ARG, "digest buffer not 16-byte aligned");
+  SCL_TRY(alias_check("merkle_root", {sclhip::alias::vec("roots_dev", roots, T, 32, true), sclhip::alias::vec("leaf_digests_dev", leaf_digests, L * T, 32, false)}));
   // levels 1, 2, .. alternate between two regions of the thread's arena; the last one goes to `roots`
   const size_t n1 = (L + 1) / 2, n2 = (n1 + 1) / 2;
   if (n1 == 1) {
@@ -331,6 +343,9 @@ int scl_hip_merkle_paths(unsigned char* path, const unsigned char* tree, size_t 
   if (!aligned16(path) || !aligned16(tree)) return fail(SCL_ERR_BAD_ARG, "digest buffer not 16-byte aligned");
   if (!leaf_index && (first_leaf >= L || (k - 1) / T >= L - first_leaf))
     return fail(SCL_ERR_INVALID_RANGE, "merkle_paths: leaf index >= L");
+  SCL_TRY(alias_check("merkle_paths", {sclhip::alias::mat("path_dev", path, merkle_depth(L), k, k, 32, true),
+                                       sclhip::alias::vec("tree_dev", tree, scl_hip_merkle_tree_bytes(L, T), 1, false),
+                                       sclhip::alias::vec("leaf_index_dev", leaf_index, k, 8, false), sclhip::alias::vec("tree_index_dev", tree_index, k, 8, false)}));
   HIP_TRY(hash_launch_paths(path, tree, L, T, leaf_index, tree_index, first_leaf, k, S(stream)));
   return SCL_OK;
 }
@@ -345,6 +360,9 @@ int scl_hip_merkle_verify(unsigned char* ok, const unsigned char* leaf_digests, 
   if (num_roots == 0) return fail(SCL_ERR_BAD_ARG, "merkle_verify: no roots");
   if (depth > 64) return fail(SCL_ERR_BAD_ARG, "merkle_verify: depth > 64");
   if (!leaf_index && depth < 64 && (leaf >> depth) != 0) return fail(SCL_ERR_INVALID_RANGE, "merkle_verify: leaf index >= 2^depth");
+  SCL_TRY(alias_check("merkle_verify", {sclhip::alias::vec("ok_dev", ok, k, 1, true), sclhip::alias::vec("leaf_digests_dev", leaf_digests, k, 32, false),
+                                        sclhip::alias::vec("leaf_index_dev", leaf_index, k, 8, false), sclhip::alias::mat("path_dev", path, depth, k, k, 32, false),
+                                        sclhip::alias::vec("roots_dev", roots, num_roots, 32, false), sclhip::alias::vec("root_index_dev", root_index, k, 8, false)}));
   HIP_TRY(hash_launch_verify(ok, leaf_digests, leaf_index, leaf, path, depth, roots, root_index, num_roots, k, S(stream)));
   return SCL_OK;
 }

@@ -17,6 +17,7 @@
 #endif
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/field.hpp"
+#include "../../include/scl_hip/detail/span.hpp"
 #include "kernels.hpp"
 #include "sha256.hpp"
 
@@ -75,6 +76,13 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
+int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
+  std::string msg;
+  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
+  return SCL_OK;
+}
+
 template <class F>
 int launch(const typename F::Ctx& ctx, unsigned char* digests, const uint64_t* a, size_t stride, size_t cols, size_t n, void* stream) {
   if (reinterpret_cast<uintptr_t>(a) & (F::LIMBS == 1 ? 7 : 15)) return fail(SCL_ERR_BAD_ARG, "element buffer misaligned");
@@ -95,6 +103,11 @@ extern "C" int scl_hip_merkle_leaves(int field, unsigned char* digests, const ui
   if (reinterpret_cast<uintptr_t>(digests) & 15) return fail(SCL_ERR_BAD_ARG, "digest buffer not 16-byte aligned");
   if (n / cols != rows) return fail(SCL_ERR_BAD_ARG, "rows * cols overflows");
   if (stride < cols) return fail(SCL_ERR_SIZE_MISMATCH, "stride < cols");
+  if (const int L = scl_hip_limbs(field); L > 0)
+    if (const int s = alias_check("merkle_leaves", {sclhip::alias::vec("digests_dev", digests, n, 32, true),
+                                                    sclhip::alias::mat("a_dev", a, rows, stride, cols, (size_t)L * 8, false)});
+        s != SCL_OK)
+      return s;
   [[maybe_unused]] const auto other_unit = [] { return fail(SCL_ERR_BAD_ARG, "field family not built into this translation unit"); };
   switch (field) {
     case SCL_M61:

@@ -10,6 +10,7 @@
 
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/secp256k1.hpp"
+#include "../../include/scl_hip/detail/span.hpp"
 
 namespace sclhip {
 namespace {
@@ -124,6 +125,14 @@ int fail(int code, const std::string& msg) {
 inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
+constexpr size_t PT_BYTES = POINT_LIMBS * sizeof(uint64_t);
+int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
+  std::string msg;
+  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
+  return SCL_OK;
+}
+
 // rows of a * G + b * H; more rows than one grid holds go to further launches
 int two_base_rows(u64* dst, size_t dst_stride, const void* gtable, const void* htable, const u64* a, size_t a_stride, const u64* b,
                   size_t b_stride, size_t rows, size_t n, hipStream_t st) {
@@ -164,6 +173,9 @@ int scl_hip_ec_mul_two_base(uint64_t* dst, const void* gtable, const void* htabl
   if (!dst || !gtable || !htable || !a || !b) return fail(SCL_ERR_BAD_ARG, "NULL operand");
   if (!aligned16(dst) || !aligned16(gtable) || !aligned16(htable) || !aligned16(a) || !aligned16(b))
     return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
+  SCL_TRY(alias_check("ec_mul_two_base", {alias::vec("dst_dev", dst, n, PT_BYTES, true), alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                          alias::vec("htable_dev", htable, scl_hip_ec_base_table_bytes(), 1, false),
+                                          alias::vec("a_dev", a, n, 32, false), alias::vec("b_dev", b, n, 32, false)}));
   return two_base_rows(dst, n, gtable, htable, a, n, b, n, 1, n, S(stream));
 }
 
@@ -175,9 +187,8 @@ int scl_hip_ec_matmul(uint64_t* dst, size_t dst_stride, const uint64_t* M, size_
   if (!aligned16(dst) || !aligned16(M) || !aligned16(points)) return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (rows > 1 && dst_stride < cols) return fail(SCL_ERR_SIZE_MISMATCH, "dst_stride < cols");
   if (p > 1 && row_stride < cols) return fail(SCL_ERR_SIZE_MISMATCH, "row_stride < cols");
-  const uint64_t* dst_end = dst + ((rows - 1) * dst_stride + cols) * POINT_LIMBS;
-  const uint64_t* points_end = points + ((p - 1) * row_stride + cols) * POINT_LIMBS;
-  if (dst < points_end && points < dst_end) return fail(SCL_ERR_BAD_ARG, "ec_matmul: dst overlaps points");
+  SCL_TRY(alias_check("ec_matmul", {alias::mat("dst_dev", dst, rows, dst_stride, cols, PT_BYTES, true), alias::mat("M_dev", M, rows, p, p, 32, false),
+                                    alias::mat("points_dev", points, p, row_stride, cols, PT_BYTES, false)}));
   return matmul_rows(dst, dst_stride, M, rows, p, points, row_stride, cols, S(stream));
 }
 
@@ -192,6 +203,12 @@ int scl_hip_pedersen_commit(uint64_t* commit, size_t commit_stride, const void* 
   if (t && commit_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "commit_stride < N");
   if (secret_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "secret_stride < N");
   if (t && share_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "share_stride < N");
+  // (of the packed share matrix, rows 0 .. t - 1 and n .. n + t - 1 are read)
+  SCL_TRY(alias_check("pedersen_commit", {alias::mat("commit_dev", commit, t + 1, commit_stride, N, PT_BYTES, true),
+                                          alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                          alias::vec("htable_dev", htable, scl_hip_ec_base_table_bytes(), 1, false),
+                                          alias::mat("secrets_dev", secrets, 2, secret_stride, N, 32, false),
+                                          alias::mat("shares_dev", shares, t ? n + t : 0, share_stride, N, 32, false)}));
   SCL_TRY(two_base_rows(commit, commit_stride, gtable, htable, secrets, 0, secrets + secret_stride * 4, 0, 1, N, S(stream)));
   // component 0 of party k - 1 is row k - 1 of the packed matrix, component 1 is n rows further on
   return two_base_rows(commit + commit_stride * POINT_LIMBS, commit_stride, gtable, htable, shares, share_stride,
@@ -207,6 +224,12 @@ int scl_hip_pedersen_verify(unsigned char* ok, const uint64_t* share, const uint
       !aligned16(scratch))
     return fail(SCL_ERR_BAD_ARG, "buffer not 16-byte aligned");
   if (t && commit_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "commit_stride < N");
+  SCL_TRY(alias_check("pedersen_verify", {alias::vec("ok_dev", ok, N, 1, true), alias::vec("share_dev", share, N, 32, false),
+                                          alias::vec("rand_dev", rand, N, 32, false), alias::mat("commit_dev", commit, t + 1, commit_stride, N, PT_BYTES, false),
+                                          alias::vec("lambda_dev", lambda, t + 1, 32, false),
+                                          alias::vec("gtable_dev", gtable, scl_hip_ec_base_table_bytes(), 1, false),
+                                          alias::vec("htable_dev", htable, scl_hip_ec_base_table_bytes(), 1, false),
+                                          alias::vec("scratch_points_dev", scratch, 2 * N, PT_BYTES, true)}));
   uint64_t* lhs = scratch;
   uint64_t* rhs = scratch + N * POINT_LIMBS;
   // the sum over the commitments is the one-row case of the matrix product: lambda is its row
