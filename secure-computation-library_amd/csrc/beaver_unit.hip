@@ -10,8 +10,6 @@
 // call stays one launch.  No LDS, no scratch; the engine is reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/scl_hip_mpc.h"
 #include "../../include/scl_hip/detail/beaver.hpp"
 
@@ -19,7 +17,6 @@ namespace sclhip {
 namespace {
 
 constexpr int BLOCK = 256;
-constexpr size_t GRID_Y_MAX = 65535;
 typedef u64 u64x2 __attribute__((ext_vector_type(2)));
 
 // W consecutive elements at p (W = 2: one-limb fields only, p 16-byte aligned)
@@ -145,104 +142,10 @@ __global__ __launch_bounds__(BLOCK) void k_beaver_finish(typename F::Ctx ctx, u6
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
+#include "unit_host.hpp"
+
 namespace {
-using namespace sclhip;
-
-thread_local std::string g_err;  // the thread's last diagnostic of THIS library
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-unsigned grid_for(size_t items) {  // one pack per lane; past 2^31 - 1 blocks the kernels' grid-stride loops take over
-  const size_t blocks = (items + BLOCK - 1) / BLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 0x7fffffffu ? 0x7fffffffu : blocks);
-}
-
-// the calling thread's Mont128 parameters: the modulus is the engine's (scl_hip_mont128_get_prime), the constants are rebuilt
-// when it changes.  The engine's stale-latch check runs first.  No prototype of scl_hip.h performs that check alone, so it is
-// reached through the cheapest host-only entry point that does: scl_hip_lagrange_basis on ONE node (two small host vectors, no
-// device work -- the one place where a call of this library allocates, on the host and for Mont128 only).  That the entry
-// point keeps the check in front of its work is pinned from this side by
-// tests/test_mpc_abi.py::test_mont128_honours_the_latch_rule, which fails the day it does not.
-int mont_ctx(Mont128::Ctx& out) {
-  uint64_t one_node[2];
-  const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
-  if (rc != SCL_OK) return fail(rc, scl_hip_last_error());
-  uint64_t p[2];
-  scl_hip_mont128_get_prime(p);
-  static thread_local Mont128::Ctx cached = {0, 0, 0, 0, 0, 0};
-  const u128 prime = ((u128)p[1] << 64) | p[0];
-  if (cached.p != prime) cached = Mont128::make_ctx(prime);
-  out = cached;
-  return SCL_OK;
-}
-
-template <class Fn>
-int with_ring_or_field(int field, Fn&& fn) {
-  if (field > 0x100 && field <= 0x100 + 128) {
-    const int K = field - 0x100;
-    if (K <= 64) return fn(Z2k64{}, Z2k64::make_ctx(K));
-    return fn(Z2k128{}, Z2k128::make_ctx(K));
-  }
-  switch (field) {
-    case SCL_M61: return fn(M61{}, M61::Ctx{});
-    case SCL_M127: return fn(M127{}, M127::Ctx{});
-    case SCL_MONT128: {
-      Mont128::Ctx ctx;
-      const int rc = mont_ctx(ctx);
-      if (rc != SCL_OK) return rc;
-      return fn(Mont128{}, ctx);
-    }
-    case SCL_GF2_128: return fn(Gf128{}, Gf128::Ctx{});
-    case SCL_SECP256K1_SCALAR: return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
-    case SCL_SECP256K1_FIELD: return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
-    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
-}
-
-bool known_tag(int field) { return (field >= SCL_M61 && field <= SCL_SECP256K1_FIELD) || (field > 0x100 && field <= 0x100 + 128); }
-
-struct Span {  // the words a matrix of `rows` rows of n elements, `stride` elements apart, covers: [lo, hi)
-  const uint64_t *lo, *hi;
-};
-Span span_of(const uint64_t* p, size_t rows, size_t stride, size_t n, size_t limbs) { return {p, p + ((rows - 1) * stride + n) * limbs}; }
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-template <class F>
-int check_align(std::initializer_list<const void*> ptrs) {
-  const uintptr_t mask = F::LIMBS == 1 ? 7 : 15;
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & mask)
-      return fail(SCL_ERR_BAD_ARG, F::LIMBS == 1 ? "pointer not 8-byte aligned" : "pointer not 16-byte aligned");
-  return SCL_OK;
-}
-
-// two one-limb elements per lane: every base 16-byte aligned, every stride that separates rows even
-template <class F>
-bool two_per_lane(std::initializer_list<const void*> ptrs, std::initializer_list<size_t> strides) {
-  if (F::LIMBS != 1) return false;
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  for (size_t s : strides)
-    if (s & 1) return false;
-  return true;
-}
-
-int need_device() {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  return SCL_OK;
-}
+bool known_tag(int field) { return is_field(field) || is_ring(field); }
 }  // namespace
 
 extern "C" {
@@ -255,9 +158,11 @@ int scl_mpc_beaver_mask(int field, uint64_t* de, size_t de_stride, const uint64_
   if (N == 0 || rows == 0) return SCL_OK;
   if (!known_tag(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
   if (!de || !x || !y || !a || !b) return fail(SCL_ERR_BAD_ARG, "NULL operand");
-  return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;  // (this library asks after its tag and NULL checks)
+  return with_ring_or_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
-    if (const int rc = check_align<F>({de, x, y, a, b})) return rc;
+    if (const int rc = check_align(nullptr, F::LIMBS, {de, x, y, a, b})) return rc;
     if (de_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "de_stride < N");
     if (op_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "op_stride < N");
     // the output has 2 rows rows of de_stride elements, an operand rows rows of op_stride: neither extent may wrap
@@ -269,7 +174,7 @@ int scl_mpc_beaver_mask(int field, uint64_t* de, size_t de_stride, const uint64_
     if (const int rc = need_device()) return rc;
     const size_t d_off = rows * de_stride * F::LIMBS;
     // (an odd rows * de_stride puts d an odd number of words past e: its rows are then 8 bytes off the 16-byte grid)
-    const bool two = two_per_lane<F>({de, x, y, a, b}, {rows > 1 ? de_stride : 0, rows > 1 ? op_stride : 0, rows * de_stride});
+    const bool two = two_per_lane(F::LIMBS, {de, x, y, a, b}, {rows > 1 ? de_stride : 0, rows > 1 ? op_stride : 0, rows * de_stride});
     for (size_t r0 = 0; r0 < rows; r0 += GRID_Y_MAX) {
       const size_t r = rows - r0 < GRID_Y_MAX ? rows - r0 : GRID_Y_MAX;
       u64* out0 = de + r0 * de_stride * F::LIMBS;
@@ -291,9 +196,11 @@ int scl_mpc_beaver_finish(int field, uint64_t* z, size_t z_stride, const uint64_
   if (N == 0 || rows == 0) return SCL_OK;
   if (!known_tag(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
   if (!z || !e || !d || !a || !b || !c) return fail(SCL_ERR_BAD_ARG, "NULL operand");
-  return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;  // (this library asks after its tag and NULL checks)
+  return with_ring_or_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
-    if (const int rc = check_align<F>({z, e, d, a, b, c})) return rc;
+    if (const int rc = check_align(nullptr, F::LIMBS, {z, e, d, a, b, c})) return rc;
     if (z_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "z_stride < N");
     if (op_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, "op_stride < N");
     if (ed_rows > rows) return fail(SCL_ERR_BAD_ARG, "beaver_finish: ed_rows > rows");
@@ -308,7 +215,7 @@ int scl_mpc_beaver_finish(int field, uint64_t* z, size_t z_stride, const uint64_
     if (overlap(out, span_of(e, 1, N, N, F::LIMBS)) || overlap(out, span_of(d, 1, N, N, F::LIMBS)))
       return fail(SCL_ERR_BAD_ARG, "beaver_finish: z overlaps e or d");
     if (const int rc = need_device()) return rc;
-    if (two_per_lane<F>({z, e, d, a, b, c}, {rows > 1 ? z_stride : 0, rows > 1 ? op_stride : 0}))
+    if (two_per_lane(F::LIMBS, {z, e, d, a, b, c}, {rows > 1 ? z_stride : 0, rows > 1 ? op_stride : 0}))
       hipLaunchKernelGGL((k_beaver_finish<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1))), dim3(BLOCK), 0, S(stream), ctx, z,
                          z_stride, e, d, a, b, c, op_stride, rows, ed_rows, N);
     else

@@ -121,28 +121,14 @@ SCL_STATE(thread_local TempArena g_temps[2]);
 }  // namespace sclhip_state
 using namespace sclhip_state;
 
+// fail / HIP_TRY / SCL_TRY / S / aligned16 / alias_check on the slot above, and make_aes_key: shared with the other units.
+// (The launch helpers of unit_host.hpp's other parts are not taken: grid_for, grid_aes4 and AES4_LAUNCH below honour the
+// "max_blocks" / "aes_blocks" knobs.)
+#define SCL_UNIT_ENGINE
+#include "unit_host.hpp"
+#include "aes_key_host.hpp"
+
 namespace {
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess)                                                                      \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP,                    \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                          \
-  } while (0)
-
-#define SCL_TRY(expr)        \
-  do {                       \
-    int s_ = (expr);         \
-    if (s_ != SCL_OK) return s_; \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // dynamic LDS bytes that cap the residency of a kernel with `static_lds` bytes of its own at `waves` waves of
 // `block` threads per CU.  A CU has 160 KiB of LDS and hands it out in granules; the granule of gfx950 is not documented
@@ -426,75 +412,6 @@ int lagrange(const typename F::Ctx& ctx, const std::vector<typename F::E>& nodes
   return SCL_OK;
 }
 
-// ---- AES-128 key schedule + T-table (FIPS-197), host side ----------------------------------------------
-struct AesHost {
-  unsigned char sbox[256];
-  AesHost() {
-    auto mul = [](unsigned a, unsigned b) {
-      unsigned r = 0;
-      while (b) {
-        if (b & 1) r ^= a;
-        a = ((a << 1) ^ ((a & 0x80) ? 0x11b : 0)) & 0xff;
-        b >>= 1;
-      }
-      return r;
-    };
-    // inverse table via generator 3: log/antilog
-    unsigned char exp[256], log[256] = {0};
-    unsigned v = 1;
-    for (int i = 0; i < 255; ++i) {
-      exp[i] = (unsigned char)v;
-      log[v] = (unsigned char)i;
-      v = mul(v, 3);
-    }
-    for (int x = 0; x < 256; ++x) {
-      unsigned inv = x ? exp[(255 - log[x]) % 255] : 0;
-      unsigned s = inv, r = inv;
-      for (int i = 0; i < 4; ++i) {
-        s = ((s << 1) | (s >> 7)) & 0xff;
-        r ^= s;
-      }
-      sbox[x] = (unsigned char)(r ^ 0x63);
-    }
-  }
-};
-
-const AesHost& aes_host() {
-  static const AesHost h;
-  return h;
-}
-
-// key = seed zero-padded / truncated to 16 bytes (prg.cc:88-101)
-void make_aes_key(const unsigned char* seed, size_t seed_len, AesKey& k) {
-  const AesHost& h = aes_host();
-  unsigned char rk[176] = {0};
-  if (seed) std::memcpy(rk, seed, seed_len > 16 ? 16 : seed_len);
-  unsigned rcon = 1;
-  for (int i = 16; i < 176; i += 4) {
-    unsigned char t[4] = {rk[i - 4], rk[i - 3], rk[i - 2], rk[i - 1]};
-    if (i % 16 == 0) {
-      const unsigned char t0 = t[0];
-      t[0] = (unsigned char)(h.sbox[t[1]] ^ rcon);
-      t[1] = h.sbox[t[2]];
-      t[2] = h.sbox[t[3]];
-      t[3] = h.sbox[t0];
-      rcon = ((rcon << 1) ^ ((rcon & 0x80) ? 0x11b : 0)) & 0xff;
-    }
-    for (int j = 0; j < 4; ++j) rk[i + j] = (unsigned char)(rk[i - 16 + j] ^ t[j]);
-  }
-  for (int w = 0; w < 44; ++w)
-    k.rk[w] = (u32)rk[4 * w] | ((u32)rk[4 * w + 1] << 8) | ((u32)rk[4 * w + 2] << 16) | ((u32)rk[4 * w + 3] << 24);
-  for (int x = 0; x < 256; ++x) {
-    const unsigned s = h.sbox[x];
-    const unsigned s2 = ((s << 1) ^ ((s & 0x80) ? 0x11b : 0)) & 0xff;
-    const unsigned s3 = s2 ^ s;
-    k.te0[x] = s2 | (s << 8) | (s << 16) | (s3 << 24);
-  }
-  aes_key_round1(k);
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // Decide the per-lane vector width for M61 rows: 2 needs 16-byte aligned bases and even strides.
 template <class F>
 int vec_width(std::initializer_list<const void*> ptrs, std::initializer_list<size_t> strides) {
@@ -513,15 +430,6 @@ int check_align(std::initializer_list<const void*> ptrs) {
   for (const void* p : ptrs)
     if (p && (reinterpret_cast<uintptr_t>(p) & mask))
       return fail(SCL_ERR_BAD_ARG, F::LIMBS == 1 ? "pointer not 8-byte aligned" : "pointer not 16-byte aligned");
-  return SCL_OK;
-}
-
-// The aliasing rule of scl_hip.h (Conventions): the call's device operands as bounding spans (detail/span.hpp); an overlap the
-// entry point does not permit is refused here, before anything is enqueued.
-using alias::Operand;
-int alias_check(const char* who, std::initializer_list<Operand> ops) {
-  std::string msg;
-  if (alias::conflict(who, ops.begin(), ops.size(), &msg) != alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
   return SCL_OK;
 }
 

@@ -12,11 +12,8 @@
 // bytes); a lane reuses its slot for every item it strides over.  docs/kernels/ecdsa.md says why projective and why this order.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/secp256k1.hpp"
-#include "../../include/scl_hip/detail/span.hpp"
 
 namespace sclhip {
 namespace {
@@ -116,41 +113,15 @@ __global__ __launch_bounds__(EBLOCK) void k_ecdsa_verify_base(unsigned char* out
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
-namespace sclhip_state {
-extern thread_local std::string g_err;  // the thread's last diagnostic (defined in the common unit of capi.hip)
-}  // namespace sclhip_state
+#define SCL_UNIT_ENGINE
+#include "unit_host.hpp"
 
 namespace {
 using namespace sclhip;
 using namespace sclhip::secp;
 
-int fail(int code, const std::string& msg) {
-  sclhip_state::g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned mul_grid(size_t n) { return (unsigned)(mul_slots(n) / EBLOCK); }
-
-// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
 constexpr size_t PT_BYTES = POINT_LIMBS * sizeof(uint64_t);
-int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
-  std::string msg;
-  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
-  return SCL_OK;
-}
-#define SCL_TRY(expr)            \
-  do {                           \
-    int s_ = (expr);             \
-    if (s_ != SCL_OK) return s_; \
-  } while (0)
 }  // namespace
 
 extern "C" {

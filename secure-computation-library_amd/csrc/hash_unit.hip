@@ -10,10 +10,7 @@
 // ones (the SoA share matrix: T = secrets, L = parties, no transpose).
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/scl_hip.h"
-#include "../../include/scl_hip/detail/span.hpp"
 #include "sha256.hpp"
 
 namespace sclhip {
@@ -182,8 +179,8 @@ hipError_t hash_launch_verify(unsigned char* ok, const unsigned char* leaf_diges
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
-// State this unit shares with the units of capi.hip (defined in the common one, see there): the thread's last diagnostic and
-// its temporary arenas.  TempArena is capi.hip's struct, member for member.
+// State this unit shares with the units of capi.hip (defined in the common one, see there): the thread's last diagnostic
+// (unit_host.hpp) and its temporary arenas.  TempArena is capi.hip's struct, member for member.
 struct TempArena {
   int device = -1;
   void* dev = nullptr;
@@ -192,31 +189,14 @@ struct TempArena {
   bool pending = false;
 };
 namespace sclhip_state {
-extern thread_local std::string g_err;
 extern thread_local TempArena g_temps[2];
 }  // namespace sclhip_state
 
+#define SCL_UNIT_ENGINE
+#include "unit_host.hpp"
+
 namespace {
 using namespace sclhip;
-
-int fail(int code, const std::string& msg) {
-  sclhip_state::g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-#define SCL_TRY(expr)            \
-  do {                           \
-    int s_ = (expr);             \
-    if (s_ != SCL_OK) return s_; \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // the discipline of capi.hip's temp_acquire / temp_release on arena 0: one buffer per host thread, kept and grown; an event
 // recorded after the last use makes the next user -- possibly on another stream -- wait for it; beyond 1 GiB it is given back
@@ -252,13 +232,6 @@ int arena_release(hipStream_t st) {
   }
   HIP_TRY(hipEventRecord(a.done, st));
   a.pending = true;
-  return SCL_OK;
-}
-
-// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
-int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
-  std::string msg;
-  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
   return SCL_OK;
 }
 

@@ -20,9 +20,6 @@
 // reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <string>
-
 #include "../../include/scl_hip_hm.h"
 #include "../../include/scl_hip/detail/hm.hpp"
 #include "kernels.hpp"
@@ -30,7 +27,6 @@
 namespace sclhip {
 namespace {
 
-constexpr size_t GRID_Y_MAX = 65535;
 constexpr int FINISH_M_MAX = 64;
 static_assert(FINISH_M_MAX <= (int)M61::ACC_TERMS, "the open of k_hm_finish never folds");
 
@@ -387,8 +383,10 @@ __global__ __launch_bounds__(BLOCK) void k_hm_finish(typename F::Ctx ctx, u64* z
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
+#define SCL_UNIT_AES
+#include "unit_host.hpp"
+
 namespace {
-using namespace sclhip;
 
 constexpr size_t FUSED_TMAX = 3;        // the fused kernel keeps 2t + 1 <= 7 coefficients in registers
 constexpr size_t PARTY_MAX = 65535;     // the node i + 1 as a small integer (GF(2^128): F::muladd_small takes 16 bits)
@@ -396,141 +394,6 @@ constexpr size_t PARTY_MAX = 65535;     // the node i + 1 as a small integer (GF
 // power table from host memory and synchronising the stream before it returns -- a call of this library never synchronises
 constexpr size_t DEG_MAX_NARROW = 48;   // 8- and 16-byte elements
 constexpr size_t DEG_MAX_WIDE = 16;     // 32-byte elements
-
-thread_local std::string g_err;  // the thread's last diagnostic of THIS library
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-unsigned grid_aes4(size_t work_items) {  // one 1024-lane workgroup per CU; the kernels grid-stride
-  const size_t blocks = (work_items + ABLOCK - 1) / ABLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > (size_t)AES4_GRID_CAP ? (size_t)AES4_GRID_CAP : blocks);
-}
-#define AES4_LAUNCH(KERN, WORK, ST, ...)                                                                            \
-  do {                                                                                                              \
-    auto kern_ = &KERN;                                                                                             \
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                AES4_LDS_BYTES));                                                                   \
-    hipLaunchKernelGGL(kern_, dim3(grid_aes4(WORK)), dim3(ABLOCK), AES4_LDS_BYTES, ST, __VA_ARGS__);                \
-    HIP_TRY(hipGetLastError());                                                                                     \
-  } while (0)
-
-unsigned grid_for(size_t items) {  // one pack per lane; past 2^31 - 1 blocks the kernels' grid-stride loops take over
-  const size_t blocks = (items + BLOCK - 1) / BLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 0x7fffffffu ? 0x7fffffffu : blocks);
-}
-
-// The AES-128 key schedule of the reference's PRG (prg.cc:88-101: key = the seed zero-padded or truncated to 16 bytes) and the
-// T-table the kernels replicate in LDS: te0[x] = (2S, S, S, 3S) from byte 0 up, S = sbox[x].  FIPS-197; the S-box from its
-// definition (inverse in GF(2^8) through the logarithms to the generator 3, then the affine map).  As csrc/triples_unit.hip.
-struct Sbox {
-  unsigned char s[256];
-  Sbox() {
-    auto xt = [](unsigned a) { return ((a << 1) ^ ((a & 0x80) ? 0x11b : 0)) & 0xff; };
-    unsigned char ex[256], lg[256] = {0};
-    unsigned v = 1;
-    for (int i = 0; i < 255; ++i) {
-      ex[i] = (unsigned char)v;
-      lg[v] = (unsigned char)i;
-      v ^= xt(v);  // v * 3
-    }
-    for (int x = 0; x < 256; ++x) {
-      const unsigned inv = x ? ex[(255 - lg[x]) % 255] : 0;
-      unsigned r = inv, rot = inv;
-      for (int i = 0; i < 4; ++i) {
-        rot = ((rot << 1) | (rot >> 7)) & 0xff;
-        r ^= rot;
-      }
-      s[x] = (unsigned char)(r ^ 0x63);
-    }
-  }
-};
-
-void make_aes_key(const unsigned char* seed, size_t seed_len, AesKey& k) {
-  static const Sbox sb;
-  unsigned char rk[176] = {0};
-  if (seed) std::memcpy(rk, seed, seed_len > 16 ? 16 : seed_len);
-  unsigned rcon = 1;
-  for (int i = 16; i < 176; i += 4) {
-    unsigned char w[4] = {rk[i - 4], rk[i - 3], rk[i - 2], rk[i - 1]};
-    if (i % 16 == 0) {
-      const unsigned char w0 = w[0];
-      w[0] = (unsigned char)(sb.s[w[1]] ^ rcon);
-      w[1] = sb.s[w[2]];
-      w[2] = sb.s[w[3]];
-      w[3] = sb.s[w0];
-      rcon = ((rcon << 1) ^ ((rcon & 0x80) ? 0x11b : 0)) & 0xff;
-    }
-    for (int j = 0; j < 4; ++j) rk[i + j] = (unsigned char)(rk[i - 16 + j] ^ w[j]);
-  }
-  for (int w = 0; w < 44; ++w)
-    k.rk[w] = (u32)rk[4 * w] | ((u32)rk[4 * w + 1] << 8) | ((u32)rk[4 * w + 2] << 16) | ((u32)rk[4 * w + 3] << 24);
-  for (int x = 0; x < 256; ++x) {
-    const unsigned s = sb.s[x], s2 = ((s << 1) ^ ((s & 0x80) ? 0x11b : 0)) & 0xff, s3 = s2 ^ s;
-    k.te0[x] = s2 | (s << 8) | (s << 16) | (s3 << 24);
-  }
-  aes_key_round1(k);
-}
-
-// the calling thread's Mont128 parameters, behind the engine's stale-latch check (reached through scl_hip_lagrange_basis on one
-// node, a host-only call, as csrc/beaver_unit.hip does and tests/test_hm_abi.py pins from this side)
-int mont_ctx(Mont128::Ctx& out) {
-  uint64_t one_node[2];
-  const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
-  if (rc != SCL_OK) return fail(rc, scl_hip_last_error());
-  uint64_t p[2];
-  scl_hip_mont128_get_prime(p);
-  static thread_local Mont128::Ctx cached = {0, 0, 0, 0, 0, 0};
-  const u128 prime = ((u128)p[1] << 64) | p[0];
-  if (cached.p != prime) cached = Mont128::make_ctx(prime);
-  out = cached;
-  return SCL_OK;
-}
-
-// the latch rule comes first among a call's checks, as in the engine: a stale thread learns of it whatever else is wrong
-int mont_latch(int field) {
-  Mont128::Ctx ctx;
-  return field == SCL_MONT128 ? mont_ctx(ctx) : SCL_OK;
-}
-
-bool is_field(int field) { return field >= SCL_M61 && field <= SCL_SECP256K1_FIELD; }
-size_t limbs_of(int field) {  // 0: not one of the six fields
-  switch (field) {
-    case SCL_M61: return 1;
-    case SCL_M127: case SCL_MONT128: case SCL_GF2_128: return 2;
-    case SCL_SECP256K1_SCALAR: case SCL_SECP256K1_FIELD: return 4;
-    default: return 0;
-  }
-}
-size_t bpe_of(size_t limbs) { return limbs >= 2 ? limbs / 2 : 1; }
-
-template <class Fn>
-int with_field(int field, Fn&& fn) {
-  switch (field) {
-    case SCL_M61: return fn(M61{}, M61::Ctx{});
-    case SCL_M127: return fn(M127{}, M127::Ctx{});
-    case SCL_MONT128: {
-      Mont128::Ctx ctx;
-      const int rc = mont_ctx(ctx);
-      if (rc != SCL_OK) return rc;
-      return fn(Mont128{}, ctx);
-    }
-    case SCL_GF2_128: return fn(Gf128{}, Gf128::Ctx{});
-    case SCL_SECP256K1_SCALAR: return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
-    case SCL_SECP256K1_FIELD: return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
-    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
-}
 
 bool fused_double(int field, size_t t, unsigned flags) {
   return !(flags & SCL_HM_TWO_PASS) && t <= FUSED_TMAX && (field == SCL_M61 || field == SCL_M127 || field == SCL_GF2_128);
@@ -540,37 +403,7 @@ size_t double_blocks(size_t limbs, size_t t) { return bpe_of(limbs) + deg_blocks
 size_t deg_max(size_t limbs) { return limbs == 4 ? DEG_MAX_WIDE : DEG_MAX_NARROW; }
 bool double_nt_ok(size_t limbs, size_t n, size_t t) { return n <= PARTY_MAX && t <= deg_max(limbs) / 2 && n > 2 * t; }
 
-struct Span {  // the words a matrix of `rows` rows of N elements, `stride` elements apart, covers: [lo, hi)
-  const uint64_t *lo, *hi;
-};
-Span span_of(const uint64_t* p, size_t rows, size_t stride, size_t N, size_t limbs) { return {p, p + ((rows - 1) * stride + N) * limbs}; }
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
-int check_align(const char* who, size_t limbs, std::initializer_list<const void*> ptrs) {
-  const uintptr_t mask = limbs == 1 ? 7 : 15;
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & mask)
-      return fail(SCL_ERR_BAD_ARG, std::string(who) + (limbs == 1 ? ": pointer not 8-byte aligned" : ": pointer not 16-byte aligned"));
-  return SCL_OK;
-}
-
-// two one-limb elements per lane: every base 16-byte aligned, every stride that separates rows even
-bool two_per_lane(size_t limbs, std::initializer_list<const void*> ptrs, std::initializer_list<size_t> strides) {
-  if (limbs != 1) return false;
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  for (size_t s : strides)
-    if (s & 1) return false;
-  return true;
-}
-
 constexpr size_t EXTENT_MAX = (size_t)1 << 60;  // elements a matrix may span: no extent below wraps
-
-int need_device() {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  return SCL_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -595,7 +428,8 @@ int scl_hm_double_share_prg(int field, uint64_t* lo_dev, uint64_t* hi_dev, size_
                             void* stream) {
   if (N == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  if (const int rc = mont_latch(field)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   if (flags & ~SCL_HM_TWO_PASS) return fail(SCL_ERR_BAD_ARG, "double_share_prg: unknown flags bit (only bit 0, two-pass, is defined)");
   const size_t L = limbs_of(field);
   if (n > PARTY_MAX) return fail(SCL_ERR_BAD_ARG, "double_share_prg: n must be at most 65535");
@@ -624,7 +458,7 @@ int scl_hm_double_share_prg(int field, uint64_t* lo_dev, uint64_t* hi_dev, size_
     const Span ss = {scratch_dev, scratch_dev + need / 8};
     if (overlap(ss, sl) || overlap(ss, sh)) return fail(SCL_ERR_BAD_ARG, "double_share_prg: the scratch overlaps a share matrix");
   }
-  return with_field(field, [&](auto f, auto ctx) -> int {
+  return with_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
     AesKey key;
@@ -658,7 +492,8 @@ int scl_hm_apply(int field, uint64_t* out_dev, size_t out_stride, size_t out_bat
                  size_t in_batch_stride, const uint64_t* M_dev, size_t ldm, size_t m, size_t n, size_t batch, size_t N, void* stream) {
   if (N == 0 || batch == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  if (const int rc = mont_latch(field)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   const size_t L = limbs_of(field);
   if (m == 0 || n == 0 || n > PARTY_MAX) return fail(SCL_ERR_BAD_ARG, "apply: m and n must be at least 1 and n at most 65535");
   if (!out_dev || !in_dev || !M_dev) return fail(SCL_ERR_BAD_ARG, "apply: NULL operand");
@@ -675,7 +510,7 @@ int scl_hm_apply(int field, uint64_t* out_dev, size_t out_stride, size_t out_bat
   const Span si = {in_dev, in_dev + ((batch - 1) * in_batch_stride + (n - 1) * in_stride + N) * L};
   if (overlap(so, si)) return fail(SCL_ERR_BAD_ARG, "apply: out overlaps in");
   if (overlap(so, span_of(M_dev, m, ldm, n, L))) return fail(SCL_ERR_BAD_ARG, "apply: out overlaps M");
-  return with_field(field, [&](auto f, auto ctx) -> int {
+  return with_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
     constexpr int R = apply_rows<F>();
@@ -727,7 +562,8 @@ int scl_hm_mul_mask(int field, uint64_t* d_dev, size_t d_stride, const uint64_t*
                     size_t op_stride, size_t rows, size_t N, void* stream) {
   if (N == 0 || rows == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  if (const int rc = mont_latch(field)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   const size_t L = limbs_of(field);
   if (!d_dev || !x_dev || !y_dev || !r2_dev) return fail(SCL_ERR_BAD_ARG, "mul_mask: NULL operand");
   if (const int rc = check_align("mul_mask", L, {d_dev, x_dev, y_dev, r2_dev})) return rc;
@@ -739,7 +575,7 @@ int scl_hm_mul_mask(int field, uint64_t* d_dev, size_t d_stride, const uint64_t*
     return fail(SCL_ERR_BAD_ARG, "mul_mask: d overlaps x or y");
   if (!(d_dev == r2_dev && d_stride == op_stride) && overlap(out, span_of(r2_dev, rows, op_stride, N, L)))
     return fail(SCL_ERR_BAD_ARG, "mul_mask: d overlaps r2 (only d == r2 with d_stride == op_stride is allowed)");
-  return with_field(field, [&](auto f, auto ctx) -> int {
+  return with_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
     const bool two = two_per_lane(L, {d_dev, x_dev, y_dev, r2_dev}, {rows > 1 ? d_stride : 0, rows > 1 ? op_stride : 0});
@@ -763,7 +599,8 @@ int scl_hm_mul_finish(int field, uint64_t* z_dev, size_t z_stride, const uint64_
                       size_t m, const uint64_t* r_dev, size_t r_stride, size_t rows, size_t N, void* stream) {
   if (N == 0 || rows == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  if (const int rc = mont_latch(field)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   const size_t L = limbs_of(field);
   if (m == 0 || m > (size_t)FINISH_M_MAX)
     return fail(SCL_ERR_BAD_ARG, "mul_finish: m must be in 1..64 (lambda travels with the launch); beyond that open with scl_hip_shamir_recover "
@@ -779,7 +616,7 @@ int scl_hm_mul_finish(int field, uint64_t* z_dev, size_t z_stride, const uint64_
   if (overlap(out, span_of(dsh_dev, m, d_stride, N, L))) return fail(SCL_ERR_BAD_ARG, "mul_finish: z overlaps dsh");
   if (!(z_dev == r_dev && z_stride == r_stride) && overlap(out, span_of(r_dev, rows, r_stride, N, L)))
     return fail(SCL_ERR_BAD_ARG, "mul_finish: z overlaps r (only z == r with z_stride == r_stride is allowed)");
-  return with_field(field, [&](auto f, auto ctx) -> int {
+  return with_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
     Lambda<F> tab;

@@ -15,11 +15,8 @@
 // The engine is reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
-#include <string>
-
 #include "../../include/scl_hip_ip.h"
 #include "../../include/scl_hip/detail/ip.hpp"
-#include "../../include/scl_hip/detail/span.hpp"
 #include "kernels.hpp"
 
 namespace sclhip {
@@ -165,92 +162,11 @@ __global__ __launch_bounds__(BLOCK) void k_ip_matmul(typename F::Ctx ctx, u64* D
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
+#include "unit_host.hpp"
+
 namespace {
-using namespace sclhip;
 
 constexpr size_t DIM_MAX = 65535;  // a, K and b of a matrix product
-
-thread_local std::string g_err;  // the thread's last diagnostic of THIS library
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-unsigned grid_for(size_t items) {  // one pack per lane; past 2^31 - 1 blocks the kernels' grid-stride loops take over
-  const size_t blocks = (items + BLOCK - 1) / BLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 0x7fffffffu ? 0x7fffffffu : blocks);
-}
-
-// the calling thread's Mont128 parameters, behind the engine's stale-latch check (reached through scl_hip_lagrange_basis on one
-// node, a host-only call, as csrc/hm_unit.hip does and tests/test_ip_abi.py pins from this side)
-int mont_ctx(Mont128::Ctx& out) {
-  uint64_t one_node[2];
-  const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
-  if (rc != SCL_OK) return fail(rc, scl_hip_last_error());
-  uint64_t p[2];
-  scl_hip_mont128_get_prime(p);
-  static thread_local Mont128::Ctx cached = {0, 0, 0, 0, 0, 0};
-  const u128 prime = ((u128)p[1] << 64) | p[0];
-  if (cached.p != prime) cached = Mont128::make_ctx(prime);
-  out = cached;
-  return SCL_OK;
-}
-
-// the latch rule comes first among a call's checks, as in the engine: a stale thread learns of it whatever else is wrong.
-// The context it yields is the call's: with_field takes it, so a call asks the engine once.
-int mont_latch(int field, Mont128::Ctx& ctx) {
-  return field == SCL_MONT128 ? mont_ctx(ctx) : SCL_OK;
-}
-
-bool is_field(int field) { return field >= SCL_M61 && field <= SCL_SECP256K1_FIELD; }
-size_t limbs_of(int field) {  // 0: not one of the six fields
-  switch (field) {
-    case SCL_M61: return 1;
-    case SCL_M127: case SCL_MONT128: case SCL_GF2_128: return 2;
-    case SCL_SECP256K1_SCALAR: case SCL_SECP256K1_FIELD: return 4;
-    default: return 0;
-  }
-}
-
-template <class Fn>
-int with_field(int field, const Mont128::Ctx& mont, Fn&& fn) {  // `mont`: what mont_latch yielded for this call
-  switch (field) {
-    case SCL_M61: return fn(M61{}, M61::Ctx{});
-    case SCL_M127: return fn(M127{}, M127::Ctx{});
-    case SCL_MONT128: return fn(Mont128{}, mont);
-    case SCL_GF2_128: return fn(Gf128{}, Gf128::Ctx{});
-    case SCL_SECP256K1_SCALAR: return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
-    case SCL_SECP256K1_FIELD: return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
-    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
-}
-
-int check_align(const char* who, size_t limbs, std::initializer_list<const void*> ptrs) {
-  const uintptr_t mask = limbs == 1 ? 7 : 15;
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & mask)
-      return fail(SCL_ERR_BAD_ARG, std::string(who) + (limbs == 1 ? ": pointer not 8-byte aligned" : ": pointer not 16-byte aligned"));
-  return SCL_OK;
-}
-
-// two one-limb elements per lane: every base 16-byte aligned, every stride that separates rows or terms even
-bool two_per_lane(size_t limbs, std::initializer_list<const void*> ptrs, std::initializer_list<size_t> strides) {
-  if (limbs != 1) return false;
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  for (size_t s : strides)
-    if (s & 1) return false;
-  return true;
-}
 
 // An operand addressed with several strides, as span.hpp sees it: ONE row of its bounding extent
 // sum_j (count_j - 1) stride_j + N elements.  false: the extent does not fit size_t.
@@ -274,12 +190,6 @@ int alias_check(const char* who, size_t esz, const void* d, size_t de, const voi
   const alias::Operand pr[2] = {ops[0], alias::vec("r2_dev", same ? nullptr : r2, re, esz, false)};
   if (alias::conflict(who, pr, 2, &msg) != alias::DISJOINT)
     return fail(SCL_ERR_BAD_ARG, msg + (msg.find("overlaps") != std::string::npos ? " (they may coincide -- the same pointer and strides -- and not overlap otherwise)" : ""));
-  return SCL_OK;
-}
-
-int need_device() {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
   return SCL_OK;
 }
 
@@ -325,7 +235,7 @@ int scl_ip_dot_mask(int field, uint64_t* d_dev, size_t d_stride, const uint64_t*
                     size_t y_term_stride, const uint64_t* r2_dev, size_t op_stride, size_t terms, size_t rows, size_t N, void* stream) {
   if (N == 0 || rows == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  Mont128::Ctx mont = {0, 0, 0, 0, 0, 0};
+  Mont128::Ctx mont = {};
   if (const int rc = mont_latch(field, mont)) return rc;
   const size_t L = limbs_of(field);
   if (terms == 0) return fail(SCL_ERR_BAD_ARG, "dot_mask: terms must be at least 1");
@@ -355,7 +265,7 @@ int scl_ip_matmul_mask(int field, uint64_t* d_dev, size_t d_stride, size_t d_bat
                        size_t r2_stride, size_t r2_batch_stride, size_t a, size_t K, size_t b, size_t batch, size_t N, void* stream) {
   if (N == 0 || batch == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  Mont128::Ctx mont = {0, 0, 0, 0, 0, 0};
+  Mont128::Ctx mont = {};
   if (const int rc = mont_latch(field, mont)) return rc;
   const size_t L = limbs_of(field);
   if (a == 0 || K == 0 || b == 0 || a > DIM_MAX || K > DIM_MAX || b > DIM_MAX)

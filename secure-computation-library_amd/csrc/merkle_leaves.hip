@@ -9,7 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
-#include <string>
 
 #include "tu_config.hpp"
 #if SCL_TU_FIELDS != 0xff
@@ -17,7 +16,6 @@
 #endif
 #include "../../include/scl_hip.h"
 #include "../../include/scl_hip/detail/field.hpp"
-#include "../../include/scl_hip/detail/span.hpp"
 #include "kernels.hpp"
 #include "sha256.hpp"
 
@@ -62,7 +60,6 @@ __global__ __launch_bounds__(BLOCK) void k_merkle_leaves(typename F::Ctx ctx, un
 }  // namespace sclhip
 
 namespace sclhip_state {  // (defined by the common unit of capi.hip)
-extern thread_local std::string g_err;
 extern thread_local Mont128::Ctx g_mont;
 extern std::mutex g_mont_default_mu;
 extern unsigned long g_mont_default_gen;
@@ -70,19 +67,10 @@ extern thread_local unsigned long g_mont_gen;
 extern thread_local bool g_mont_own;
 }  // namespace sclhip_state
 
+#define SCL_UNIT_ENGINE
+#include "unit_host.hpp"
+
 namespace {
-int fail(int code, const std::string& msg) {
-  sclhip_state::g_err = msg;
-  return code;
-}
-
-// the aliasing rule of scl_hip.h (Conventions), checked before anything is enqueued: detail/span.hpp
-int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> ops) {
-  std::string msg;
-  if (sclhip::alias::conflict(who, ops.begin(), ops.size(), &msg) != sclhip::alias::DISJOINT) return fail(SCL_ERR_BAD_ARG, msg);
-  return SCL_OK;
-}
-
 template <class F>
 int launch(const typename F::Ctx& ctx, unsigned char* digests, const uint64_t* a, size_t stride, size_t cols, size_t n, void* stream) {
   if (reinterpret_cast<uintptr_t>(a) & (F::LIMBS == 1 ? 7 : 15)) return fail(SCL_ERR_BAD_ARG, "element buffer misaligned");

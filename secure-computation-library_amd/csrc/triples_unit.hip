@@ -17,9 +17,6 @@
 // None of them reads device memory.  The engine is reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <string>
-
 #include "../../include/scl_hip_prep.h"
 #include "kernels.hpp"
 
@@ -198,8 +195,10 @@ __global__ __launch_bounds__(ABLOCK) void k_triple_coeff_rows(typename F::Ctx ct
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
+#define SCL_UNIT_AES
+#include "unit_host.hpp"
+
 namespace {
-using namespace sclhip;
 
 constexpr size_t FUSED_TMAX = 7;        // the fused Shamir kernel keeps t + 1 <= 8 coefficients in registers
 constexpr size_t PARTY_MAX = 65535;     // Shamir: the node i + 1 as a small integer (GF(2^128): F::muladd_small takes 16 bits)
@@ -207,147 +206,6 @@ constexpr size_t PARTY_MAX = 65535;     // Shamir: the node i + 1 as a small int
 // power table from host memory and synchronising the stream before it returns -- a call of this library never synchronises
 constexpr size_t T_MAX_NARROW = 48;     // 8- and 16-byte elements
 constexpr size_t T_MAX_WIDE = 16;       // 32-byte elements
-
-thread_local std::string g_err;  // the thread's last diagnostic of THIS library
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-unsigned grid_aes4(size_t work_items) {  // one 1024-lane workgroup per CU; the kernels grid-stride
-  const size_t blocks = (work_items + ABLOCK - 1) / ABLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > (size_t)AES4_GRID_CAP ? (size_t)AES4_GRID_CAP : blocks);
-}
-#define AES4_LAUNCH(KERN, WORK, ST, ...)                                                                            \
-  do {                                                                                                              \
-    auto kern_ = &KERN;                                                                                             \
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                AES4_LDS_BYTES));                                                                   \
-    hipLaunchKernelGGL(kern_, dim3(grid_aes4(WORK)), dim3(ABLOCK), AES4_LDS_BYTES, ST, __VA_ARGS__);                \
-    HIP_TRY(hipGetLastError());                                                                                     \
-  } while (0)
-
-// The AES-128 key schedule of the reference's PRG (prg.cc:88-101: key = the seed zero-padded or truncated to 16 bytes) and the
-// T-table the kernels replicate in LDS: te0[x] = (2S, S, S, 3S) from byte 0 up, S = sbox[x].  FIPS-197; the S-box from its
-// definition (inverse in GF(2^8) through the logarithms to the generator 3, then the affine map).
-struct Sbox {
-  unsigned char s[256];
-  Sbox() {
-    auto xt = [](unsigned a) { return ((a << 1) ^ ((a & 0x80) ? 0x11b : 0)) & 0xff; };
-    unsigned char ex[256], lg[256] = {0};
-    unsigned v = 1;
-    for (int i = 0; i < 255; ++i) {
-      ex[i] = (unsigned char)v;
-      lg[v] = (unsigned char)i;
-      v ^= xt(v);  // v * 3
-    }
-    for (int x = 0; x < 256; ++x) {
-      const unsigned inv = x ? ex[(255 - lg[x]) % 255] : 0;
-      unsigned r = inv, rot = inv;
-      for (int i = 0; i < 4; ++i) {
-        rot = ((rot << 1) | (rot >> 7)) & 0xff;
-        r ^= rot;
-      }
-      s[x] = (unsigned char)(r ^ 0x63);
-    }
-  }
-};
-
-void make_aes_key(const unsigned char* seed, size_t seed_len, AesKey& k) {
-  static const Sbox sb;
-  unsigned char rk[176] = {0};
-  if (seed) std::memcpy(rk, seed, seed_len > 16 ? 16 : seed_len);
-  unsigned rcon = 1;
-  for (int i = 16; i < 176; i += 4) {
-    unsigned char w[4] = {rk[i - 4], rk[i - 3], rk[i - 2], rk[i - 1]};
-    if (i % 16 == 0) {
-      const unsigned char w0 = w[0];
-      w[0] = (unsigned char)(sb.s[w[1]] ^ rcon);
-      w[1] = sb.s[w[2]];
-      w[2] = sb.s[w[3]];
-      w[3] = sb.s[w0];
-      rcon = ((rcon << 1) ^ ((rcon & 0x80) ? 0x11b : 0)) & 0xff;
-    }
-    for (int j = 0; j < 4; ++j) rk[i + j] = (unsigned char)(rk[i - 16 + j] ^ w[j]);
-  }
-  for (int w = 0; w < 44; ++w)
-    k.rk[w] = (u32)rk[4 * w] | ((u32)rk[4 * w + 1] << 8) | ((u32)rk[4 * w + 2] << 16) | ((u32)rk[4 * w + 3] << 24);
-  for (int x = 0; x < 256; ++x) {
-    const unsigned s = sb.s[x], s2 = ((s << 1) ^ ((s & 0x80) ? 0x11b : 0)) & 0xff, s3 = s2 ^ s;
-    k.te0[x] = s2 | (s << 8) | (s << 16) | (s3 << 24);
-  }
-  aes_key_round1(k);
-}
-
-// the calling thread's Mont128 parameters, behind the engine's stale-latch check (reached through scl_hip_lagrange_basis on one
-// node, a host-only call, as csrc/beaver_unit.hip does and tests/test_prep_abi.py pins from this side)
-int mont_ctx(Mont128::Ctx& out) {
-  uint64_t one_node[2];
-  const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
-  if (rc != SCL_OK) return fail(rc, scl_hip_last_error());
-  uint64_t p[2];
-  scl_hip_mont128_get_prime(p);
-  static thread_local Mont128::Ctx cached = {0, 0, 0, 0, 0, 0};
-  const u128 prime = ((u128)p[1] << 64) | p[0];
-  if (cached.p != prime) cached = Mont128::make_ctx(prime);
-  out = cached;
-  return SCL_OK;
-}
-
-// the latch rule comes first among a call's checks, as in the engine: a stale thread learns of it whatever else is wrong
-int mont_latch(int field) {
-  Mont128::Ctx ctx;
-  return field == SCL_MONT128 ? mont_ctx(ctx) : SCL_OK;
-}
-
-bool is_ring(int field) { return field > 0x100 && field <= 0x100 + 128; }
-bool is_field(int field) { return field >= SCL_M61 && field <= SCL_SECP256K1_FIELD; }
-size_t limbs_of(int field) {  // 0: unknown tag
-  if (is_ring(field)) return field - 0x100 <= 64 ? 1 : 2;
-  switch (field) {
-    case SCL_M61: return 1;
-    case SCL_M127: case SCL_MONT128: case SCL_GF2_128: return 2;
-    case SCL_SECP256K1_SCALAR: case SCL_SECP256K1_FIELD: return 4;
-    default: return 0;
-  }
-}
-size_t bpe_of(size_t limbs) { return limbs >= 2 ? limbs / 2 : 1; }
-
-template <class Fn>
-int with_field(int field, Fn&& fn) {
-  switch (field) {
-    case SCL_M61: return fn(M61{}, M61::Ctx{});
-    case SCL_M127: return fn(M127{}, M127::Ctx{});
-    case SCL_MONT128: {
-      Mont128::Ctx ctx;
-      const int rc = mont_ctx(ctx);
-      if (rc != SCL_OK) return rc;
-      return fn(Mont128{}, ctx);
-    }
-    case SCL_GF2_128: return fn(Gf128{}, Gf128::Ctx{});
-    case SCL_SECP256K1_SCALAR: return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
-    case SCL_SECP256K1_FIELD: return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
-    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
-}
-template <class Fn>
-int with_ring_or_field(int field, Fn&& fn) {
-  if (is_ring(field)) {
-    const int K = field - 0x100;
-    if (K <= 64) return fn(Z2k64{}, Z2k64::make_ctx(K));
-    return fn(Z2k128{}, Z2k128::make_ctx(K));
-  }
-  return with_field(field, fn);
-}
 
 bool fused_shamir(int field, size_t t, unsigned flags) {
   return !(flags & SCL_PREP_TWO_PASS) && t <= FUSED_TMAX && (field == SCL_M61 || field == SCL_M127 || field == SCL_GF2_128);
@@ -359,21 +217,12 @@ bool additive_n_ok(size_t n) { return n >= 2 && n <= 0x7fffffffu / 4; }
 size_t shamir_t_max(size_t limbs) { return limbs == 4 ? T_MAX_WIDE : T_MAX_NARROW; }
 bool shamir_nt_ok(size_t limbs, size_t n, size_t t) { return n >= 1 && n <= PARTY_MAX && t <= shamir_t_max(limbs); }
 
-struct Span {  // the words a matrix of `rows` rows of N elements, `stride` elements apart, covers: [lo, hi)
-  const uint64_t *lo, *hi;
-};
-Span span_of(const uint64_t* p, size_t rows, size_t stride, size_t N, size_t limbs) { return {p, p + ((rows - 1) * stride + N) * limbs}; }
-bool overlap(const Span& a, const Span& b) { return a.lo < b.hi && b.lo < a.hi; }
-
 // what both deal calls check alike, in the order the header lists it; B = blocks per triple
 int check_matrices(const char* who, size_t limbs, uint64_t* a, uint64_t* b, uint64_t* c, size_t stride, size_t N, size_t n, uint64_t B,
                    uint64_t counter0) {
   const std::string w(who);
   if (!a || !b || !c) return fail(SCL_ERR_BAD_ARG, w + ": NULL operand");
-  const uintptr_t mask = limbs == 1 ? 7 : 15;
-  for (const uint64_t* p : {a, b, c})
-    if (reinterpret_cast<uintptr_t>(p) & mask)
-      return fail(SCL_ERR_BAD_ARG, w + (limbs == 1 ? ": pointer not 8-byte aligned" : ": pointer not 16-byte aligned"));
+  if (const int rc = check_align(who, limbs, {a, b, c})) return rc;
   if (stride < N) return fail(SCL_ERR_SIZE_MISMATCH, w + ": stride < N");
   if (n > ((size_t)1 << 60) / stride / limbs) return fail(SCL_ERR_BAD_ARG, w + ": n * stride overflows");
   const Span sa = span_of(a, n, stride, N, limbs), sb = span_of(b, n, stride, N, limbs), sc = span_of(c, n, stride, N, limbs);
@@ -384,11 +233,6 @@ int check_matrices(const char* who, size_t limbs, uint64_t* a, uint64_t* b, uint
   return SCL_OK;
 }
 
-int need_device() {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  return SCL_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -397,7 +241,7 @@ int scl_prep_abi_version(void) { return SCL_PREP_ABI_VERSION; }
 const char* scl_prep_last_error(void) { return g_err.c_str(); }
 
 size_t scl_prep_triple_blocks(int field, int scheme, size_t n, size_t t) {
-  const size_t L = limbs_of(field);
+  const size_t L = limbs_of(field, true);
   if (scheme == SCL_PREP_ADDITIVE) return L && additive_n_ok(n) ? additive_blocks(L, n) : 0;
   if (scheme == SCL_PREP_SHAMIR) return is_field(field) && shamir_nt_ok(L, n, t) ? shamir_blocks(L, t) : 0;
   return 0;
@@ -412,13 +256,14 @@ size_t scl_prep_triples_scratch_bytes(int field, size_t N, size_t n, size_t t, u
 int scl_prep_triples_additive_prg(int field, uint64_t* a_dev, uint64_t* b_dev, uint64_t* c_dev, size_t stride, size_t N, size_t n,
                                   const unsigned char* seed_host, size_t seed_len, uint64_t counter0, void* stream) {
   if (N == 0) return SCL_OK;
-  const size_t L = limbs_of(field);
+  const size_t L = limbs_of(field, true);
   if (!L) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  if (const int rc = mont_latch(field)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   if (!additive_n_ok(n)) return fail(SCL_ERR_BAD_ARG, "triples_additive_prg: n must be >= 2 (and below 2^29)");
   const uint64_t B = additive_blocks(L, n);
   if (const int rc = check_matrices("triples_additive_prg", L, a_dev, b_dev, c_dev, stride, N, n, B, counter0)) return rc;
-  return with_ring_or_field(field, [&](auto f, auto ctx) -> int {
+  return with_ring_or_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
     AesKey key;
@@ -446,7 +291,8 @@ int scl_prep_triples_shamir_prg(int field, uint64_t* a_dev, uint64_t* b_dev, uin
                                 unsigned flags, void* stream) {
   if (N == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  if (const int rc = mont_latch(field)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   if (flags & ~SCL_PREP_TWO_PASS) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: unknown flags bit (only bit 0, two-pass, is defined)");
   const size_t L = limbs_of(field);
   if (!shamir_nt_ok(L, n, t))
@@ -466,7 +312,7 @@ int scl_prep_triples_shamir_prg(int field, uint64_t* a_dev, uint64_t* b_dev, uin
     for (const uint64_t* p : {a_dev, b_dev, c_dev})
       if (overlap(ss, span_of(p, n, stride, N, L))) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: the scratch overlaps a share matrix");
   }
-  return with_field(field, [&](auto f, auto ctx) -> int {
+  return with_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
     AesKey key;

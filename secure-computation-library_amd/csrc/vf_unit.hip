@@ -17,19 +17,14 @@
 // The engine is reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <string>
 #include <type_traits>
 
 #include "../../include/scl_hip_vf.h"
 #include "../../include/scl_hip/detail/vf.hpp"
-#include "../../include/scl_hip/detail/span.hpp"
 #include "kernels.hpp"
 
 namespace sclhip {
 namespace {
-
-constexpr size_t GRID_Y_MAX = 65535;
 
 template <class F>
 constexpr int pack_w() {
@@ -245,134 +240,12 @@ __global__ __launch_bounds__(BLOCK) void k_vf_finish(typename F::Ctx ctx, u64* o
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
+#define SCL_UNIT_AES
+#include "unit_host.hpp"
+
 namespace {
-using namespace sclhip;
 
 static_assert(VF_THREADS_STREAM == BLOCK && VF_THREADS_AES == ABLOCK && VF_GRID_AES == AES4_GRID_CAP, "vf.hpp restates the launch constants of kernels.hpp");
-
-thread_local std::string g_err;  // the thread's last diagnostic of THIS library
-
-int fail(int code, const std::string& msg) {
-  g_err = msg;
-  return code;
-}
-#define HIP_TRY(expr)                                                                                                        \
-  do {                                                                                                                       \
-    hipError_t e_ = (expr);                                                                                                  \
-    if (e_ != hipSuccess)                                                                                                    \
-      return fail(e_ == hipErrorNoDevice ? SCL_ERR_NO_DEVICE : SCL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-  } while (0)
-
-inline hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
-
-unsigned grid_aes4(size_t work_items) {  // one 1024-lane workgroup per CU; the kernels grid-stride
-  const size_t blocks = (work_items + ABLOCK - 1) / ABLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > (size_t)AES4_GRID_CAP ? (size_t)AES4_GRID_CAP : blocks);
-}
-#define AES4_LAUNCH_GRID(KERN, GRID, ST, ...)                                                                       \
-  do {                                                                                                              \
-    auto kern_ = &KERN;                                                                                             \
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                AES4_LDS_BYTES));                                                                   \
-    hipLaunchKernelGGL(kern_, GRID, dim3(ABLOCK), AES4_LDS_BYTES, ST, __VA_ARGS__);                                 \
-    HIP_TRY(hipGetLastError());                                                                                     \
-  } while (0)
-
-// The AES-128 key schedule of the reference's PRG (prg.cc:88-101: key = the seed zero-padded or truncated to 16 bytes) and the
-// T-table the kernels replicate in LDS: te0[x] = (2S, S, S, 3S) from byte 0 up, S = sbox[x].  FIPS-197; the S-box from its
-// definition (inverse in GF(2^8) through the logarithms to the generator 3, then the affine map).  As csrc/hm_unit.hip.
-struct Sbox {
-  unsigned char s[256];
-  Sbox() {
-    auto xt = [](unsigned a) { return ((a << 1) ^ ((a & 0x80) ? 0x11b : 0)) & 0xff; };
-    unsigned char ex[256], lg[256] = {0};
-    unsigned v = 1;
-    for (int i = 0; i < 255; ++i) {
-      ex[i] = (unsigned char)v;
-      lg[v] = (unsigned char)i;
-      v ^= xt(v);  // v * 3
-    }
-    for (int x = 0; x < 256; ++x) {
-      const unsigned inv = x ? ex[(255 - lg[x]) % 255] : 0;
-      unsigned r = inv, rot = inv;
-      for (int i = 0; i < 4; ++i) {
-        rot = ((rot << 1) | (rot >> 7)) & 0xff;
-        r ^= rot;
-      }
-      s[x] = (unsigned char)(r ^ 0x63);
-    }
-  }
-};
-
-void make_aes_key(const unsigned char* seed, size_t seed_len, AesKey& k) {
-  static const Sbox sb;
-  unsigned char rk[176] = {0};
-  if (seed) std::memcpy(rk, seed, seed_len > 16 ? 16 : seed_len);
-  unsigned rcon = 1;
-  for (int i = 16; i < 176; i += 4) {
-    unsigned char w[4] = {rk[i - 4], rk[i - 3], rk[i - 2], rk[i - 1]};
-    if (i % 16 == 0) {
-      const unsigned char w0 = w[0];
-      w[0] = (unsigned char)(sb.s[w[1]] ^ rcon);
-      w[1] = sb.s[w[2]];
-      w[2] = sb.s[w[3]];
-      w[3] = sb.s[w0];
-      rcon = ((rcon << 1) ^ ((rcon & 0x80) ? 0x11b : 0)) & 0xff;
-    }
-    for (int j = 0; j < 4; ++j) rk[i + j] = (unsigned char)(rk[i - 16 + j] ^ w[j]);
-  }
-  for (int w = 0; w < 44; ++w)
-    k.rk[w] = (u32)rk[4 * w] | ((u32)rk[4 * w + 1] << 8) | ((u32)rk[4 * w + 2] << 16) | ((u32)rk[4 * w + 3] << 24);
-  for (int x = 0; x < 256; ++x) {
-    const unsigned s = sb.s[x], s2 = ((s << 1) ^ ((s & 0x80) ? 0x11b : 0)) & 0xff, s3 = s2 ^ s;
-    k.te0[x] = s2 | (s << 8) | (s << 16) | (s3 << 24);
-  }
-  aes_key_round1(k);
-}
-
-// the calling thread's Mont128 parameters, behind the engine's stale-latch check (reached through scl_hip_lagrange_basis on one
-// node, a host-only call, as csrc/ip_unit.hip does and tests/test_vf_abi.py pins from this side)
-int mont_ctx(Mont128::Ctx& out) {
-  uint64_t one_node[2];
-  const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
-  if (rc != SCL_OK) return fail(rc, scl_hip_last_error());
-  uint64_t p[2];
-  scl_hip_mont128_get_prime(p);
-  static thread_local Mont128::Ctx cached = {0, 0, 0, 0, 0, 0};
-  const u128 prime = ((u128)p[1] << 64) | p[0];
-  if (cached.p != prime) cached = Mont128::make_ctx(prime);
-  out = cached;
-  return SCL_OK;
-}
-
-bool is_field(int field) { return field >= SCL_M61 && field <= SCL_SECP256K1_FIELD; }
-size_t limbs_of(int field) {  // 0: not one of the six fields
-  switch (field) {
-    case SCL_M61: return 1;
-    case SCL_M127: case SCL_MONT128: case SCL_GF2_128: return 2;
-    case SCL_SECP256K1_SCALAR: case SCL_SECP256K1_FIELD: return 4;
-    default: return 0;
-  }
-}
-
-template <class Fn>
-int with_field(int field, const Mont128::Ctx& mont, Fn&& fn) {
-  switch (field) {
-    case SCL_M61: return fn(M61{}, M61::Ctx{});
-    case SCL_M127: return fn(M127{}, M127::Ctx{});
-    case SCL_MONT128: return fn(Mont128{}, mont);
-    case SCL_GF2_128: return fn(Gf128{}, Gf128::Ctx{});
-    case SCL_SECP256K1_SCALAR: return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
-    case SCL_SECP256K1_FIELD: return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
-    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
-}
-
-int need_device() {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  return SCL_OK;
-}
 
 size_t round16(size_t b) { return (b + 15) & ~(size_t)15; }
 // columns between the coefficient rows of the two-pass path: a Mersenne61 row starts 16-byte aligned
@@ -407,9 +280,8 @@ int combine_common(const char* who, bool prg, int field, uint64_t* out_dev, size
                    size_t seed_len, uint64_t counter0, uint64_t* scratch_dev, size_t scratch_bytes, void* stream) {
   if (rows == 0) return SCL_OK;
   if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  Mont128::Ctx mont = {0, 0, 0, 0, 0, 0};
-  if (field == SCL_MONT128)
-    if (const int rc = mont_ctx(mont)) return rc;
+  Mont128::Ctx mont = {};
+  if (const int rc = mont_latch(field, mont)) return rc;
   const std::string w = who;
   const size_t L = limbs_of(field), esz = 8 * L;
   if (reps == 0 || reps > VF_REPS_MAX) return fail(SCL_ERR_BAD_ARG, w + ": reps must be at least 1 and at most 4");

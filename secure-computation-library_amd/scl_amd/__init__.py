@@ -12,18 +12,13 @@ and trailing dimension `limbs(field)`; a share matrix is SoA `[party][secret][li
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 import torch  # imported BEFORE the extension so both share torch's libamdhip64 (same SONAME)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libscl_hip.so")
-if not os.path.exists(_SO):
-    raise ImportError(
-        f"{_SO} is missing: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()' or make -C secure-computation-library_amd/csrc)")
-lib = C.CDLL(_SO)
+from scl_amd import _abi
+
+lib, _SO = _abi.load("scl_hip")
 
 M61, M127, MONT128, GF2_128, SECP256K1_SCALAR, SECP256K1_FIELD = 0, 1, 2, 3, 4, 5
 
@@ -46,15 +41,10 @@ OK, ERR_SIZE_MISMATCH, ERR_ZERO_INVERSE, ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ER
 
 
 def _declare_prototypes():
-    """argtypes / restype of every entry point, read from the prototypes of include/scl_hip.h (the boundary's one
-    source of truth): a forgotten c_size_t wrap or a swapped argument is then a ctypes.ArgumentError, not a wild
-    pointer.  Every pointer parameter is c_void_p (accepts ints, data_ptr() wrappers, bytes, byref() and None)."""
-    import re
-    import warnings
-    # the repository's header, or the copy the csrc Makefile leaves next to the .so (a package moved without the tree)
-    candidates = [os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "scl_hip.h"), os.path.join(_HERE, "scl_hip.h")]
-    hdr = next((c for c in candidates if os.path.exists(c)), None)
-    if hdr is None:
+    """argtypes / restype of every entry point, read from the prototypes of include/scl_hip.h (_abi.declare).  Two things are
+    the engine's own: without a header the import goes on with a warning, and a header without a version macro is accepted."""
+    if _abi.find_header("scl_hip.h") is None:
+        import warnings
         # no header to read: result types only (status ints, the two size_t / string getters); arguments unchecked
         warnings.warn("scl_amd: include/scl_hip.h not found beside the package; ctypes argument checking is off")
         for name, ret in (("scl_hip_last_error", C.c_char_p), ("scl_hip_status_message", C.c_char_p),
@@ -63,37 +53,7 @@ def _declare_prototypes():
             if hasattr(lib, name):
                 getattr(lib, name).restype = ret
         return 0
-    src = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
-    # the boundary's version first: a library built from an older header fails HERE, with a message that says so, not at the
-    # lookup of a symbol it does not have
-    want = re.search(r"#define\s+SCL_HIP_ABI_VERSION\s+(\d+)", src)
-    lib.scl_hip_abi_version.restype = C.c_int
-    have = lib.scl_hip_abi_version()
-    if want and have != int(want.group(1)):
-        raise ImportError(f"scl_amd: {_SO} implements ABI version {have}, {hdr} declares {want.group(1)}: rebuild the extension "
-                          "(make -C secure-computation-library_amd/csrc)")
-    scalars = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "unsigned": C.c_uint,
-               "float": C.c_float}
-    rets = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
-    n = 0
-    for m in re.finditer(r"\b(int|size_t|const char\s*\*)\s*(scl_hip_\w+)\s*\(([^;{]*?)\)\s*;", src):
-        ret, name, params = m.group(1).replace(" ", "").replace("constchar*", "const char*"), m.group(2), m.group(3)
-        fn = getattr(lib, name)
-        fn.restype = rets[ret]
-        argt = []
-        for prm in [x.strip() for x in params.split(",")]:
-            if prm in ("void", ""):
-                continue
-            if "*" in prm or "[" in prm:
-                argt.append(C.c_void_p)
-            else:
-                base = re.sub(r"\bconst\b", "", prm).split()
-                if base[0] not in scalars:
-                    raise ImportError(f"scl_amd: {name}: parameter type {base[0]!r} in {hdr} has no ctypes mapping here")
-                argt.append(scalars[base[0]])
-        fn.argtypes = argt
-        n += 1
-    return n
+    return _abi.declare(lib, _SO, "scl_hip.h", "scl_hip_", "SCL_HIP_ABI_VERSION", "scl_amd", version_optional=True)
 
 
 _NPROTO = _declare_prototypes()

@@ -10,64 +10,20 @@ HIP stream go to the C ABI; there is no CPU or torch fallback.  Tensors are thos
 from __future__ import annotations
 
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import torch
 
 import scl_amd as _scl  # the engine first: libscl_hip_hm.so links against libscl_hip.so and finds it loaded
+from scl_amd import _abi
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_SO = os.path.join(_HERE, "libscl_hip_hm.so")
-if not os.path.exists(_SO):
-    raise ImportError(
-        f"{_SO} is missing: build the HIP extension first "
-        "(python -c 'import __graft_entry__ as g; g.build()' or make -C secure-computation-library_amd/csrc)")
-lib = C.CDLL(_SO)
+lib, _SO = _abi.load("scl_hip_hm")
 
 TWO_PASS = 1                # flags bit 0 of double_share
 
 
-def _declare_prototypes():
-    """argtypes / restype of every entry point from the prototypes of include/scl_hip_hm.h, as scl_amd does for scl_hip.h;
-    the boundary's version is compared BEFORE any other symbol is looked up"""
-    candidates = [os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "scl_hip_hm.h"), os.path.join(_HERE, "scl_hip_hm.h")]
-    hdr = next((c for c in candidates if os.path.exists(c)), None)
-    if hdr is None:
-        raise ImportError("scl_amd.hm: include/scl_hip_hm.h not found beside the package")
-    src = re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
-    want = re.search(r"#define\s+SCL_HM_ABI_VERSION\s+(\d+)", src)
-    lib.scl_hm_abi_version.restype = C.c_int
-    lib.scl_hm_abi_version.argtypes = []
-    have = lib.scl_hm_abi_version()
-    if not want or have != int(want.group(1)):
-        raise ImportError(f"scl_amd.hm: {_SO} implements ABI version {have}, {hdr} declares {want.group(1) if want else '?'}: "
-                          "rebuild the extension (make -C secure-computation-library_amd/csrc)")
-    scalars = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "unsigned": C.c_uint}
-    rets = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
-    n = 0
-    for m in re.finditer(r"\b(int|size_t|const char\s*\*)\s*(scl_hm_\w+)\s*\(([^;{]*?)\)\s*;", src):
-        ret, name, params = m.group(1).replace(" ", "").replace("constchar*", "const char*"), m.group(2), m.group(3)
-        fn = getattr(lib, name)
-        fn.restype = rets[ret]
-        argt = []
-        for prm in [x.strip() for x in params.split(",")]:
-            if prm in ("void", ""):
-                continue
-            if "*" in prm or "[" in prm:
-                argt.append(C.c_void_p)
-            else:
-                base = re.sub(r"\bconst\b", "", prm).split()
-                if base[0] not in scalars:
-                    raise ImportError(f"scl_amd.hm: {name}: parameter type {base[0]!r} in {hdr} has no ctypes mapping here")
-                argt.append(scalars[base[0]])
-        fn.argtypes = argt
-        n += 1
-    return n
-
-
-_NPROTO = _declare_prototypes()
+# argtypes / restype of every entry point from the prototypes of include/scl_hip_hm.h; the boundary's version is compared first
+_NPROTO = _abi.declare(lib, _SO, "scl_hip_hm.h", "scl_hm_", "SCL_HM_ABI_VERSION", "scl_amd.hm")
 
 
 def _chk(status: int):

@@ -102,10 +102,13 @@ def test_the_engine_is_its_only_project_dependency():
 
 
 def test_version_and_prototypes_come_from_the_header(vf):
-    """the binding compares the version before it looks up another symbol (scl_amd/vf.py) and types every prototype"""
+    """the binding compares the version before it looks up another symbol (scl_amd/vf.py through the one loader, scl_amd/_abi.py)
+    and types every prototype"""
     assert vf.lib.scl_vf_abi_version() == 1 and re.search(r"#define\s+SCL_VF_ABI_VERSION\s+1\b", header())
-    src = open(os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "vf.py")).read()
-    assert src.index("lib.scl_vf_abi_version()") < src.index("for m in re.finditer")
+    pkg = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd")
+    assert '_abi.declare(lib, _SO, "scl_hip_vf.h", "scl_vf_", "SCL_VF_ABI_VERSION"' in open(os.path.join(pkg, "vf.py")).read()
+    src = open(os.path.join(pkg, "_abi.py")).read()
+    assert src.index('getattr(lib, prefix + "abi_version")') < src.index("have = version()") < src.index("for m in re.finditer")
     assert vf._NPROTO == len(declared_symbols()) == 7
     for name in declared_symbols():
         assert getattr(vf.lib, name).argtypes is not None, name
