@@ -41,6 +41,14 @@ inline void check(int status) {
   if (status != SCL_OK) raise(status);
 }
 
+/// a status of an extension library (libscl_hip_mpc.so, _prep, _hm, _ip, _vf) -> the same exceptions, with THAT library's
+/// diagnostic: `last_error` is its scl_X_last_error.  "Vec sizes mismatch" stays the reference's exception and text.
+inline void check(int status, const char* (*last_error)(void)) {
+  if (status == SCL_OK) return;
+  if (status == SCL_ERR_SIZE_MISMATCH) raise(status);
+  throw std::runtime_error(std::string(scl_hip_status_message(status)) + ": " + last_error());
+}
+
 }  // namespace scl::hip::detail
 
 #endif

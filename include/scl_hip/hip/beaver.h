@@ -33,11 +33,7 @@ struct Triple {
 
 namespace beaver_detail {
 /// a status of libscl_hip_mpc.so -> the exception of detail/call.h, with THAT library's diagnostic
-inline void check(int status) {
-  if (status == SCL_OK) return;
-  if (status == SCL_ERR_SIZE_MISMATCH) detail::raise(status);
-  throw std::runtime_error(std::string(scl_hip_status_message(status)) + ": " + scl_mpc_last_error());
-}
+inline void check(int status) { detail::check(status, scl_mpc_last_error); }
 }  // namespace beaver_detail
 
 /// What the parties send each other: rows 0..parties-1 are their shares of e, rows parties..2 parties-1 their shares of d.

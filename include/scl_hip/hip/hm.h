@@ -23,11 +23,7 @@ namespace scl::hip {
 
 namespace hm_detail {
 /// a status of libscl_hip_hm.so -> the exception of detail/call.h, with THAT library's diagnostic
-inline void check(int status) {
-  if (status == SCL_OK) return;
-  if (status == SCL_ERR_SIZE_MISMATCH) detail::raise(status);
-  throw std::runtime_error(std::string(scl_hip_status_message(status)) + ": " + scl_hm_last_error());
-}
+inline void check(int status) { detail::check(status, scl_hm_last_error); }
 }  // namespace hm_detail
 
 /// every party's shares of N secrets, twice: lo of degree t, hi of degree 2t

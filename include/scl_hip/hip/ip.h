@@ -18,11 +18,7 @@ namespace scl::hip {
 
 namespace ip_detail {
 /// a status of libscl_hip_ip.so -> the exception of detail/call.h, with THAT library's diagnostic
-inline void check(int status) {
-  if (status == SCL_OK) return;
-  if (status == SCL_ERR_SIZE_MISMATCH) detail::raise(status);
-  throw std::runtime_error(std::string(scl_hip_status_message(status)) + ": " + scl_ip_last_error());
-}
+inline void check(int status) { detail::check(status, scl_ip_last_error); }
 }  // namespace ip_detail
 
 /// Every party's [d]_2t = sum_{k<terms} [x_k]_t [y_k]_t + [R]_2t in one launch.  x and y hold the terms one after another:

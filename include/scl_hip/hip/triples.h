@@ -21,11 +21,7 @@ namespace scl::hip {
 
 namespace triples_detail {
 /// a status of libscl_hip_prep.so -> the exception of detail/call.h, with THAT library's diagnostic
-inline void check(int status) {
-  if (status == SCL_OK) return;
-  if (status == SCL_ERR_SIZE_MISMATCH) detail::raise(status);
-  throw std::runtime_error(std::string(scl_hip_status_message(status)) + ": " + scl_prep_last_error());
-}
+inline void check(int status) { detail::check(status, scl_prep_last_error); }
 }  // namespace triples_detail
 
 /// AES blocks one triple consumes: additive (t ignored) or Shamir (n, t); what a PRG advances by per triple

@@ -17,11 +17,7 @@ namespace scl::hip {
 
 namespace vf_detail {
 /// a status of libscl_hip_vf.so -> the exception of detail/call.h, with THAT library's diagnostic
-inline void check(int status) {
-  if (status == SCL_OK) return;
-  if (status == SCL_ERR_SIZE_MISMATCH) detail::raise(status);
-  throw std::runtime_error(std::string(scl_hip_status_message(status)) + ": " + scl_vf_last_error());
-}
+inline void check(int status) { detail::check(status, scl_vf_last_error); }
 inline DeviceBuffer scratch(int tag, std::size_t rows, std::size_t reps, std::size_t N, unsigned flags, std::size_t* bytes) {
   *bytes = scl_vf_scratch_bytes(tag, rows, reps, N, flags);
   if (rows && !*bytes) throw std::runtime_error(std::string(scl_hip_status_message(SCL_ERR_BAD_ARG)) + ": combine: reps outside 1..4, or rows * reps * N overflows");

@@ -15,81 +15,8 @@
 #include "scl_hip/detail/hm.hpp"
 using namespace sclhip;
 
-static long g_bad = 0, g_checks = 0;
-static void check(bool ok, const char* what, const char* op, long at) {
-  ++g_checks;
-  if (!ok) {
-    if (g_bad < 20) std::printf("MISMATCH %s %s case %ld\n", what, op, at);
-    ++g_bad;
-  }
-}
-
-static u64 g_state = 0x243F6A8885A308D3ull;
-static u64 next64() {  // splitmix64
-  u64 z = (g_state += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-static u128 next128() {
-  const u64 lo = next64();
-  return ((u128)next64() << 64) | lo;
-}
-
-// per field: a uniform canonical element and the extreme ones
-template <class F>
-struct Gen;
-template <>
-struct Gen<M61> {
-  static u64 rnd(const M61::Ctx&) { return next64() % M61::P; }
-  static std::vector<u64> pool(const M61::Ctx&) {
-    const u64 p = M61::P;
-    return {0, 1, p - 1, p - 2, (p - 1) / 2, (p + 1) / 2};
-  }
-};
-template <>
-struct Gen<M127> {
-  static u128 rnd(const M127::Ctx&) { return next128() % M127::P(); }
-  static std::vector<u128> pool(const M127::Ctx&) {
-    const u128 p = M127::P();
-    return {0, 1, p - 1, p - 2, (p - 1) / 2, (p + 1) / 2};
-  }
-};
-template <>
-struct Gen<Mont128> {
-  static u128 rnd(const Mont128::Ctx& c) { return next128() % c.p; }
-  static std::vector<u128> pool(const Mont128::Ctx& c) {
-    const u128 p = c.p;
-    return {0, 1, p - 1, p - 2, (p - 1) / 2, (p - 1) / 2 + 1, c.one};
-  }
-};
-template <>
-struct Gen<Gf128> {
-  static u128 rnd(const Gf128::Ctx&) { return next128(); }
-  static std::vector<u128> pool(const Gf128::Ctx&) {
-    const u128 ones = ~(u128)0;
-    return {0, 1, ones, ones - 1, ones >> 1, (u128)1 << 127};
-  }
-};
-template <class PRM>
-struct Gen<Mont256<PRM>> {
-  typedef Mont256<PRM> F;
-  static typename F::E rnd(const typename F::Ctx&) {
-    typename F::E r = F::make(next64(), next64(), next64(), next64());
-    if (F::geq_p(r)) F::sub_n(r, r, F::prime());  // both primes exceed 2^255: one subtraction lands below p
-    return r;
-  }
-  static std::vector<typename F::E> pool(const typename F::Ctx& c) {
-    const typename F::E p = F::prime(), one = F::make(1, 0, 0, 0), two = F::make(2, 0, 0, 0);
-    typename F::E pm1, pm2, half, half1;
-    F::sub_n(pm1, p, one);
-    F::sub_n(pm2, p, two);
-    half = F::make((pm1.w[0] >> 1) | (pm1.w[1] << 63), (pm1.w[1] >> 1) | (pm1.w[2] << 63), (pm1.w[2] >> 1) | (pm1.w[3] << 63),
-                   pm1.w[3] >> 1);
-    F::add_n(half1, half, one);
-    return {F::zero(), one, pm1, pm2, half, half1, F::one(c)};
-  }
-};
+#define CHECK_SEED 0x243F6A8885A308D3ull
+#include "check.hpp"
 
 // sum_i k[i] x[i] through hm_mac_step against reduced mul and add
 template <class F>
@@ -147,6 +74,5 @@ int main() {
   run_field<Gf128>(Gf128::Ctx{}, "GF(2^128)", uniform);
   run_field<Secp256k1Scalar>(Secp256k1Scalar::Ctx{}, "secp256k1 order", uniform);
   run_field<Secp256k1Field>(Secp256k1Field::Ctx{}, "secp256k1 field", uniform);
-  std::printf("%ld checks, %ld mismatches\n", g_checks, g_bad);
-  return g_bad != 0;
+  return summary();
 }

@@ -15,64 +15,8 @@
 #include "scl_hip/detail/ip.hpp"
 using namespace sclhip;
 
-static long g_bad = 0, g_checks = 0;
-static void check(bool ok, const char* what, const char* op, long at) {
-  ++g_checks;
-  if (!ok) {
-    if (g_bad < 20) std::printf("MISMATCH %s %s case %ld\n", what, op, at);
-    ++g_bad;
-  }
-}
-
-static u64 g_state = 0x13198A2E03707344ull;
-static u64 next64() {  // splitmix64
-  u64 z = (g_state += 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-static u128 next128() {
-  const u64 lo = next64();
-  return ((u128)next64() << 64) | lo;
-}
-
-// per field: a uniform canonical element and the largest one
-template <class F>
-struct Gen;
-template <>
-struct Gen<M61> {
-  static u64 rnd(const M61::Ctx&) { return next64() % M61::P; }
-  static u64 top(const M61::Ctx&) { return M61::P - 1; }
-};
-template <>
-struct Gen<M127> {
-  static u128 rnd(const M127::Ctx&) { return next128() % M127::P(); }
-  static u128 top(const M127::Ctx&) { return M127::P() - 1; }
-};
-template <>
-struct Gen<Mont128> {
-  static u128 rnd(const Mont128::Ctx& c) { return next128() % c.p; }
-  static u128 top(const Mont128::Ctx& c) { return c.p - 1; }
-};
-template <>
-struct Gen<Gf128> {
-  static u128 rnd(const Gf128::Ctx&) { return next128(); }
-  static u128 top(const Gf128::Ctx&) { return ~(u128)0; }
-};
-template <class PRM>
-struct Gen<Mont256<PRM>> {
-  typedef Mont256<PRM> F;
-  static typename F::E rnd(const typename F::Ctx&) {
-    typename F::E r = F::make(next64(), next64(), next64(), next64());
-    if (F::geq_p(r)) F::sub_n(r, r, F::prime());  // both primes exceed 2^255: one subtraction lands below p
-    return r;
-  }
-  static typename F::E top(const typename F::Ctx&) {
-    typename F::E r;
-    F::sub_n(r, F::prime(), F::make(1, 0, 0, 0));
-    return r;
-  }
-};
+#define CHECK_SEED 0x13198A2E03707344ull
+#include "check.hpp"
 
 // sum_k x[k] y[k] (+ r2): ip_dot_one, the step by hand with its count watched, and a 2 x 2 tile under one count
 template <class F>
@@ -150,6 +94,5 @@ int main() {
   run_field<Gf128>(Gf128::Ctx{}, "GF(2^128)");
   run_field<Secp256k1Scalar>(Secp256k1Scalar::Ctx{}, "secp256k1 order");
   run_field<Secp256k1Field>(Secp256k1Field::Ctx{}, "secp256k1 field");
-  std::printf("%ld checks, %ld mismatches\n", g_checks, g_bad);
-  return g_bad != 0;
+  return summary();
 }

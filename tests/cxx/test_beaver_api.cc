@@ -14,17 +14,9 @@
 #include <scl_hip/scl.h>
 #include <scl_hip/hip/beaver.h>
 
-using namespace scl;
+#include "check.hpp"
 
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__);        \
-    }                                                                             \
-  } while (0)
+using namespace scl;
 
 template <typename T>
 static std::vector<T> randoms(std::size_t N, util::PRG& prg) {
@@ -110,6 +102,5 @@ int main() {
   shamir_round_trip<F61>("Mersenne61", 4099);
   two_party_additive<F61>("Mersenne61", 257);
   two_party_additive<Scalar>("secp256k1_order", 65);
-  std::printf("%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary();
 }

@@ -30,29 +30,15 @@
 
 #include "scl_hip/scl.h"
 
+#include "check.hpp"
+
 using namespace scl;
 namespace secp = sclhip::secp;
-
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__);        \
-    }                                                                             \
-  } while (0)
 
 using Curve = util::ECDSA::PublicKey;
 using Scalar = util::ECDSA::SecretKey;
 using Sig = util::Signature<util::ECDSA>;
 
-static std::vector<unsigned char> unhex(const std::string& s) {
-  std::vector<unsigned char> out;
-  if (s == "-") return out;
-  for (std::size_t i = 0; i + 1 < s.size(); i += 2) out.push_back((unsigned char)std::stoul(s.substr(i, 2), nullptr, 16));
-  return out;
-}
 static std::string hex(const unsigned char* p, std::size_t n) {
   std::string s;
   char b[3];
@@ -91,12 +77,6 @@ static sclhip::U256 limbsOf(const Scalar& s) {
   sclhip::U256 r;
   s.toLimbs(r.w);
   return r;
-}
-static std::vector<std::string> split(const std::string& s, char sep) {
-  std::vector<std::string> out;
-  std::stringstream ss(s);
-  for (std::string item; std::getline(ss, item, sep);) out.push_back(item);
-  return out;
 }
 static std::string seedOf(std::string s) {
   for (char& c : s)

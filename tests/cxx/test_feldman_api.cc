@@ -25,27 +25,14 @@
 
 #include "scl_hip/scl.h"
 
-using namespace scl;
+#include "check.hpp"
 
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__);        \
-    }                                                                             \
-  } while (0)
+using namespace scl;
 
 using Curve = math::EC<math::ec::Secp256k1>;
 using Field = Curve::Field;
 using Scalar = Curve::ScalarField;
 
-static std::vector<unsigned char> unhex(const std::string& s) {
-  std::vector<unsigned char> out;
-  for (std::size_t i = 0; i + 1 < s.size(); i += 2) out.push_back((unsigned char)std::stoul(s.substr(i, 2), nullptr, 16));
-  return out;
-}
 static std::string image(const Curve& p) {
   unsigned char buf[65];
   REQUIRE(seri::Serializer<Curve>::write(p, buf) == 65);
@@ -61,12 +48,6 @@ static Curve pointOf(const std::string& hex) {
   Curve p;
   REQUIRE(seri::Serializer<Curve>::read(p, unhex(hex).data()) == 65);
   return p;
-}
-static std::vector<std::string> split(const std::string& s, char sep) {
-  std::vector<std::string> out;
-  std::stringstream ss(s);
-  for (std::string item; std::getline(ss, item, sep);) out.push_back(item);
-  return out;
 }
 static Curve randomPoint(util::PRG& prg) { return Curve::generator() * Scalar::random(prg); }
 

@@ -20,37 +20,11 @@
 #include <scl_hip/hip/hm.h>
 #include <scl_hip/ss/double_share.h>
 
+#include "check.hpp"
+
 using namespace scl;
 
 static const char* SEED = "hm fixture";
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__); \
-    }                                                                             \
-  } while (0)
-
-template <typename T>
-static std::string image(const T& v) {  // the FF::write image, in hex
-  unsigned char buf[64];
-  v.write(buf);
-  std::string s;
-  char h[3];
-  for (std::size_t i = 0; i < T::byteSize(); ++i) {
-    std::snprintf(h, sizeof h, "%02x", buf[i]);
-    s += h;
-  }
-  return s;
-}
-template <typename T>
-static void elems(const char* key, const std::vector<T>& v, const char* tail) {
-  std::printf("\"%s\":[", key);
-  for (std::size_t i = 0; i < v.size(); ++i) std::printf("%s\"%s\"", i ? "," : "", image(v[i]).c_str());
-  std::printf("]%s", tail);
-}
 
 template <typename T>
 static void hims(const char* field, bool first) {
@@ -90,20 +64,6 @@ static void double_runs(const char* field, bool first) {
     first = false;
   }
   double_run<T>(field, 4, 1, 3, false);
-}
-
-// the elements' limbs, for the per-element forms of detail/hm.hpp
-template <typename T, class F>
-static typename F::E limbs(const T& v) {
-  std::uint64_t w[4] = {0, 0, 0, 0};
-  v.toLimbs(w);
-  return F::ld(w);
-}
-template <typename T, class F>
-static T element(const typename F::E& e) {
-  std::uint64_t w[4] = {0, 0, 0, 0};
-  F::st(w, e);
-  return T::fromLimbs(w);
 }
 
 template <typename T, class F>
@@ -209,8 +169,7 @@ static int host() {
   protocol<F61, sclhip::M61>("m61", 10, 3, false);
   protocol<Scalar, sclhip::Secp256k1Scalar>("secp256k1_scalar", 4, 1, false);
   std::printf("]}\n");
-  std::fprintf(stderr, "%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary(stderr);
 }
 
 // ---- on the device -----------------------------------------------------------------------------------------------------------
@@ -277,8 +236,7 @@ static int gpu() {
   device_equals_host<F61>("Mersenne61", 33, 9, 4);           // two-pass
   multiply<F61>("Mersenne61", 38, 10, 3);  // (scl_hip_stream_copy moves 16-byte units: an even N for one-limb rows)
   multiply<Scalar>("secp256k1_order", 9, 4, 1);
-  std::printf("%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary();
 }
 
 int main(int argc, char** argv) {

@@ -20,50 +20,9 @@
 #include <scl_hip/hip/ip.h>
 #include <scl_hip/ss/double_share.h>
 
+#include "check.hpp"
+
 using namespace scl;
-
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__); \
-    }                                                                             \
-  } while (0)
-
-template <typename T>
-static std::string image(const T& v) {  // the FF::write image, in hex
-  unsigned char buf[64];
-  v.write(buf);
-  std::string s;
-  char h[3];
-  for (std::size_t i = 0; i < T::byteSize(); ++i) {
-    std::snprintf(h, sizeof h, "%02x", buf[i]);
-    s += h;
-  }
-  return s;
-}
-template <typename T>
-static void elems(const char* key, const std::vector<T>& v, const char* tail) {
-  std::printf("\"%s\":[", key);
-  for (std::size_t i = 0; i < v.size(); ++i) std::printf("%s\"%s\"", i ? "," : "", image(v[i]).c_str());
-  std::printf("]%s", tail);
-}
-
-// the elements' limbs, for the per-element forms of detail/ip.hpp and detail/hm.hpp
-template <typename T, class F>
-static typename F::E limbs(const T& v) {
-  std::uint64_t w[4] = {0, 0, 0, 0};
-  v.toLimbs(w);
-  return F::ld(w);
-}
-template <typename T, class F>
-static T element(const typename F::E& e) {
-  std::uint64_t w[4] = {0, 0, 0, 0};
-  F::st(w, e);
-  return T::fromLimbs(w);
-}
 
 template <typename T>
 struct Inputs {
@@ -176,8 +135,7 @@ static int host() {
   matrix<F127, sclhip::M127>("m127", false);
   matrix<Scalar, sclhip::Secp256k1Scalar>("secp256k1_scalar", false);
   std::printf("]}\n");
-  std::fprintf(stderr, "%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary(stderr);
 }
 
 // ---- on the device -----------------------------------------------------------------------------------------------------------
@@ -278,8 +236,7 @@ static int gpu() {
   matmul<F61, sclhip::M61>("Mersenne61", 1, 65, 1, 38, 4);  // the inner-product route
   matmul<F127, sclhip::M127>("Mersenne127", 3, 4, 5, 33, 3);
   matmul<Scalar, sclhip::Secp256k1Scalar>("secp256k1_order", 3, 3, 3, 9, 4);
-  std::printf("%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary();
 }
 
 int main(int argc, char** argv) {

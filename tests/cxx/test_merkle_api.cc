@@ -20,27 +20,13 @@
 
 #include "scl_hip/scl.h"
 
-using namespace scl;
+#include "check.hpp"
 
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__);        \
-    }                                                                             \
-  } while (0)
+using namespace scl;
 
 using Digest = util::Digest<256>;
 using StrTree = util::MerkleTree<util::Sha256, std::string_view>;
 
-static std::vector<unsigned char> unhex(const std::string& s) {
-  std::vector<unsigned char> out;
-  if (s == "-") return out;
-  for (std::size_t i = 0; i + 1 < s.size(); i += 2) out.push_back((unsigned char)std::stoul(s.substr(i, 2), nullptr, 16));
-  return out;
-}
 static Digest digestOf(const std::string& hex) {
   Digest d{};
   const auto b = unhex(hex);

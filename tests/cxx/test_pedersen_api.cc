@@ -24,17 +24,9 @@
 
 #include "scl_hip/scl.h"
 
-using namespace scl;
+#include "check.hpp"
 
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                       \
-  do {                                                                     \
-    ++g_checks;                                                            \
-    if (!(__VA_ARGS__)) {                                                  \
-      ++g_fail;                                                            \
-      std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__); \
-    }                                                                      \
-  } while (0)
+using namespace scl;
 
 using EC = math::EC<math::ec::Secp256k1>;
 using FF = EC::ScalarField;
@@ -42,11 +34,6 @@ using Pair = math::Array<FF, 2>;
 
 static const EC h = EC::generator() * FF(42);
 
-static std::vector<unsigned char> unhex(const std::string& s) {
-  std::vector<unsigned char> out;
-  for (std::size_t i = 0; i + 1 < s.size(); i += 2) out.push_back((unsigned char)std::stoul(s.substr(i, 2), nullptr, 16));
-  return out;
-}
 static std::string hexOf(const unsigned char* p, std::size_t n) {
   std::string s;
   char b[3];
@@ -83,12 +70,6 @@ static EC pointOf(const std::string& hex) {
   return p;
 }
 static FF scalarOf(const std::string& hex) { return FF::read(unhex(hex).data()); }
-static std::vector<std::string> split(const std::string& s, char sep) {
-  std::vector<std::string> out;
-  std::stringstream ss(s);
-  for (std::string item; std::getline(ss, item, sep);) out.push_back(item);
-  return out;
-}
 // test_pedersen.cc:77-92
 static std::vector<std::vector<ss::PedersenShare<EC>>> getShares(std::size_t n, std::size_t t) {
   auto prg = util::PRG::create("Pedersen apply");

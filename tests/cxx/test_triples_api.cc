@@ -20,37 +20,12 @@
 #include <scl_hip/hip/triples.h>
 #include <scl_hip/ss/triples.h>
 
+#include "check.hpp"
+
 using namespace scl;
 
 static const char* SEED = "triples fixture";
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__); \
-    }                                                                             \
-  } while (0)
 
-template <typename T>
-static std::string image(const T& v) {  // the FF::write image, in hex
-  unsigned char buf[64];
-  v.write(buf);
-  std::string s;
-  char h[3];
-  for (std::size_t i = 0; i < T::byteSize(); ++i) {
-    std::snprintf(h, sizeof h, "%02x", buf[i]);
-    s += h;
-  }
-  return s;
-}
-template <typename T>
-static void elems(const char* key, const std::vector<T>& v, const char* tail) {
-  std::printf("\"%s\":[", key);
-  for (std::size_t i = 0; i < v.size(); ++i) std::printf("%s\"%s\"", i ? "," : "", image(v[i]).c_str());
-  std::printf("]%s", tail);
-}
 template <typename T>
 static std::vector<T> column(const std::vector<hip::Triple<T>>& tr, int which) {
   std::vector<T> v;
@@ -142,8 +117,7 @@ static int host() {
   shamir_runs<Scalar>("secp256k1_scalar");
   shamir_runs<Field>("secp256k1_field");
   std::printf("]}\n");
-  std::fprintf(stderr, "%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary(stderr);
 }
 
 // ---- on the device -----------------------------------------------------------------------------------------------------------
@@ -203,8 +177,7 @@ static int gpu() {
   multiply<F61>("Mersenne61", 257, 2, -1);
   multiply<F61>("Mersenne61", 257, 10, 3);
   multiply<Scalar>("secp256k1_order", 65, 5, 2);
-  std::printf("%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary();
 }
 
 int main(int argc, char** argv) {

@@ -22,36 +22,10 @@
 #include <scl_hip/hip/vf.h>
 #include <scl_hip/ss/vf.h>
 
+#include "check.hpp"
+
 using namespace scl;
 
-static int g_fail = 0, g_checks = 0;
-#define REQUIRE(...)                                                              \
-  do {                                                                            \
-    ++g_checks;                                                                   \
-    if (!(__VA_ARGS__)) {                                                         \
-      ++g_fail;                                                                   \
-      std::fprintf(stderr, "FAILED %s:%d: %s\n", __FILE__, __LINE__, #__VA_ARGS__); \
-    }                                                                             \
-  } while (0)
-
-template <typename T>
-static std::string image(const T& v) {  // the FF::write image, in hex
-  unsigned char buf[64];
-  v.write(buf);
-  std::string s;
-  char h[3];
-  for (std::size_t i = 0; i < T::byteSize(); ++i) {
-    std::snprintf(h, sizeof h, "%02x", buf[i]);
-    s += h;
-  }
-  return s;
-}
-template <typename T>
-static void elems(const char* key, const math::Vector<T>& v, const char* tail) {
-  std::printf("\"%s\":[", key);
-  for (std::size_t i = 0; i < v.size(); ++i) std::printf("%s\"%s\"", i ? "," : "", image(v[i]).c_str());
-  std::printf("]%s", tail);
-}
 template <typename T>
 static void rows(const char* key, const std::vector<math::Vector<T>>& m, const char* tail) {
   std::printf("\"%s\":[", key);
@@ -61,20 +35,6 @@ static void rows(const char* key, const std::vector<math::Vector<T>>& m, const c
     std::printf("]");
   }
   std::printf("]%s", tail);
-}
-
-// the elements' limbs, for the per-element forms of detail/vf.hpp
-template <typename T, class F>
-static typename F::E limbs(const T& v) {
-  std::uint64_t w[4] = {0, 0, 0, 0};
-  v.toLimbs(w);
-  return F::ld(w);
-}
-template <typename T, class F>
-static T element(const typename F::E& e) {
-  std::uint64_t w[4] = {0, 0, 0, 0};
-  F::st(w, e);
-  return T::fromLimbs(w);
 }
 
 // ss::combine of one row, held against vf_combine_one (the function the kernels accumulate with) on the limbs
@@ -240,8 +200,7 @@ static int host() {
   product<F127, sclhip::M127>("m127", false);
   product<Scalar, sclhip::Secp256k1Scalar>("secp256k1_scalar", false);
   std::printf("]}\n");
-  std::fprintf(stderr, "%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary(stderr);
 }
 
 // ---- on the device -----------------------------------------------------------------------------------------------------------
@@ -347,8 +306,7 @@ static int gpu() {
   round_trip<Scalar, sclhip::Secp256k1Scalar>("secp256k1_order", 4, 33, 4);  // two launches of two repetitions
   degree_gpu<F61>("Mersenne61", 257, 10, 3);
   degree_gpu<Scalar>("secp256k1_order", 33, 7, 3);
-  std::printf("%d checks, %d failures\n", g_checks, g_fail);
-  return g_fail != 0;
+  return summary();
 }
 
 int main(int argc, char** argv) {

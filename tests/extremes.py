@@ -53,6 +53,22 @@ def gf_mul(a: int, b: int) -> int:
     return r
 
 
+def refl(v: int) -> int:
+    """a 128-bit block with its bits reversed: between GCM's blocks (bit 0 first) and this field's integers"""
+    return int(format(v, "0128b")[::-1], 2)
+
+
+def spec_mul(X: int, Y: int) -> int:
+    """the multiplication of the GCM specification as it is written there (Algorithm 1: right shifts, R = e1 || 0^120) on
+    blocks as big-endian integers"""
+    Z, V = 0, X
+    for i in range(128):
+        if (Y >> (127 - i)) & 1:
+            Z ^= V
+        V = (V >> 1) ^ (0xe1 << 120) if V & 1 else V >> 1
+    return Z
+
+
 def gf_inv(a: int) -> int:
     """a^(2^128 - 2) by square-and-multiply on the bit-serial multiplier"""
     r, e, base = 1, (1 << 128) - 2, a

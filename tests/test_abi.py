@@ -3,12 +3,12 @@ include/scl_hip.h declares, and its host-only entry points (tables, messages) be
 reference.  No kernels are launched here."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from abi_support import ENGINE, declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -19,14 +19,8 @@ def scl():
     return scl_amd
 
 
-def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "scl_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_hip_\w+)\s*\(", src)))
-
-
 def test_every_declared_symbol_is_exported(scl):
-    names = declared_symbols()
+    names = declared_symbols(ENGINE)
     assert len(names) >= 40
     missing = [n for n in names if not hasattr(scl.lib, n)]
     assert not missing, missing
@@ -40,7 +34,7 @@ def test_nothing_but_the_declared_symbols_is_exported(scl):
     so = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "libscl_hip.so")
     out = subprocess.run(["nm", "-D", "--defined-only", so], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert exported == set(declared_symbols()), sorted(exported ^ set(declared_symbols()))
+    assert exported == set(declared_symbols(ENGINE)), sorted(exported ^ set(declared_symbols(ENGINE)))
 
 
 def test_metadata_and_messages(scl):
@@ -203,7 +197,7 @@ def test_recover_detect_refuses_a_node_range_it_does_not_have(scl):
 def test_prototypes_come_from_the_header(scl):
     """every entry point has argtypes / restype taken from include/scl_hip.h: a Python int in a pointer slot of the wrong
     kind or a missing argument is an error at the call, not a wild pointer on the device"""
-    names = declared_symbols()
+    names = declared_symbols(ENGINE)
     assert scl._NPROTO == len(names)
     assert scl.lib.scl_hip_shamir_share.argtypes[2] is C.c_size_t and scl.lib.scl_hip_wire_size.restype is C.c_size_t
     with pytest.raises((C.ArgumentError, TypeError)):

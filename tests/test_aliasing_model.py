@@ -14,6 +14,8 @@ import subprocess
 
 import pytest
 
+from abi_support import ENGINE, declared_symbols
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CXX = os.path.join(ROOT, "tests", "cxx")
 
@@ -51,9 +53,8 @@ def device_operands(params):
 
 
 def test_the_parser_reads_the_header_as_test_abi_does():
-    import test_abi
     protos = prototypes()
-    assert sorted(protos) == test_abi.declared_symbols()
+    assert sorted(protos) == declared_symbols(ENGINE)
     params, comment = protos["scl_hip_ec_mul"]
     assert [n for _, n in params] == ["dst_dev", "points_dev", "scalars_dev", "scratch_dev", "n", "stream"]
     assert device_operands(params) == (["dst_dev", "scratch_dev"], ["dst_dev", "points_dev", "scalars_dev", "scratch_dev"])

@@ -5,9 +5,9 @@ import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.path.join(ROOT, "tests", "cxx")
-BIN = os.path.join(CXX, "_build", "test_scl_api")
+from cxx_support import BUILD, CXX, ROOT, host_check
+
+BIN = os.path.join(BUILD, "test_scl_api")
 
 
 def _build():
@@ -35,7 +35,7 @@ def test_cxx_open_over_a_world_of_threads():
     """hip::Communicator / hip::open / hip::openByPartialSums -- the C++ mirror of the C ABI's open step -- with worlds of 2, 3,
     4 and 8: the ranks are std::threads of the test binary on this one GPU, RCCL is tests/cxx/fake_rccl.cc bound through
     SCL_HIP_RCCL_LIBRARY (an all-gather = rendezvous + device-to-device copies).  Every rank must end with every secret."""
-    fake = os.path.join(CXX, "_build", "libfake_rccl.so")
+    fake = os.path.join(BUILD, "libfake_rccl.so")
     exe = _build()
     assert os.path.exists(fake)
     r = subprocess.run([exe, "--open-world"], capture_output=True, text=True, env=dict(os.environ, SCL_HIP_RCCL_LIBRARY=fake),
@@ -46,7 +46,7 @@ def test_cxx_open_over_a_world_of_threads():
 
 def _per_secret(args):
     subprocess.run(["make", "-s", "-C", CXX], check=True)
-    r = subprocess.run([os.path.join(CXX, "_build", "bench_per_secret")] + args, capture_output=True, text=True)
+    r = subprocess.run([os.path.join(BUILD, "bench_per_secret")] + args, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("per_secret")][-1]
     return {k: v for k, v in (kv.split("=") for kv in line.split()[1:])}
@@ -107,12 +107,7 @@ def test_mont128_small_node_fold_against_long_arithmetic(tmp_path):
     a quotient estimate sharp enough for ONE conditional subtraction -- on two million sums with extreme operands and five
     full-width moduli, against a 192-bit sum reduced bit by bit (tests/cxx/mont128_fold_check.cc).  The GPU half of the same
     arithmetic: tests/test_plugin_field_pins.py (Python big integers) and every Mont128 sharing test."""
-    exe = str(tmp_path / "mont128_fold_check")
-    b = subprocess.run(["g++", "-std=c++20", "-O2", f"-I{ROOT}/include", "-o", exe, os.path.join(CXX, "mont128_fold_check.cc")],
-                       capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and "0 mismatches" in r.stdout, r.stdout + r.stderr
+    host_check(tmp_path, "mont128_fold_check.cc", "mont128_fold_check", want=("0 mismatches",))
 
 
 def test_mont128_interleaved_product_against_long_arithmetic(tmp_path):
@@ -122,25 +117,14 @@ def test_mont128_interleaved_product_against_long_arithmetic(tmp_path):
     (tests/cxx/mont_mul_check.cc, 840 k products); Mont256::mul over both secp256k1 primes
     the same way against the limb-by-limb form it replaced (600 k products).  The kernels compile the same function; the reference's own values for it:
     tests/golden/golden_mont128.json."""
-    exe = str(tmp_path / "mont_mul_check")
-    b = subprocess.run(["g++", "-std=c++20", "-O2", f"-I{ROOT}/include", "-o", exe, os.path.join(CXX, "mont_mul_check.cc")],
-                       capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout + r.stderr
+    host_check(tmp_path, "mont_mul_check.cc", "mont_mul_check")
 
 
 def test_gf2_128_host_arithmetic_against_a_bit_serial_multiplier(tmp_path):
     """Gf128::mul (4-bit-window comb), sqr (bit spread + fold) and inv (Itoh-Tsujii chain) of detail/field.hpp -- the code behind
     FF<GF2_128> on the host and, for sqr / inv, in the kernels -- against a shift-xor multiplier and the 254-product ladder
     (tests/cxx/gf128_host_check.cc): 400 k comparisons, corners included.  CPU only."""
-    exe = str(tmp_path / "gf128_host_check")
-    b = subprocess.run(["g++", "-std=c++20", "-O2", "-w", f"-I{ROOT}/include", "-o", exe, os.path.join(CXX, "gf128_host_check.cc")],
-                       capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout
-
+    host_check(tmp_path, "gf128_host_check.cc", "gf128_host_check", ("-O2", "-w"))
 
 
 def test_lazy_accumulators_at_their_term_bounds(tmp_path):
@@ -149,9 +133,4 @@ def test_lazy_accumulators_at_their_term_bounds(tmp_path):
     p - 1, all-ones limbs and the digit-extreme Mersenne61 words, against double-and-add on the field's reduced add; and the
     muladd_small_lazy steps of Mersenne61 and Mersenne127 chained at the edges of their stated input ranges
     (tests/cxx/lazy_acc_check.cc).  The kernels compile the same functions; tests/test_gpu_extremes.py drives them there."""
-    exe = str(tmp_path / "lazy_acc_check")
-    b = subprocess.run(["g++", "-std=c++20", "-O2", "-w", f"-I{ROOT}/include", "-o", exe, os.path.join(CXX, "lazy_acc_check.cc")],
-                       capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout + r.stderr
+    host_check(tmp_path, "lazy_acc_check.cc", "lazy_acc_check", ("-O2", "-w"))

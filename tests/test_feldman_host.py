@@ -1,127 +1,18 @@
 """Feldman VSS, the host half: the C++ mirror's math::EC<ec::Secp256k1> and ss::feldman* (tests/cxx/test_feldman_api.cc) against
-what the REFERENCE computed (tests/golden/golden_feldman.json), and an independent Python model -- big-integer affine secp256k1
-and Lagrange interpolation over the group order -- that pins the same fixture by something that is neither the reference nor
+what the REFERENCE computed (tests/golden/golden_feldman.json), and an independent Python model (tests/secp256k1_model.py) -- big-integer affine
+secp256k1 and Lagrange interpolation over the group order -- that pins the same fixture by something that is neither the reference nor
 this code.  The model also checks the kernels in tests/test_gpu_feldman.py."""
-import json
-import os
 import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.path.join(ROOT, "tests", "cxx")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_feldman.json")
-
-# ---- the model: y^2 = x^3 + 7 over P, affine, None = infinity (SEC 2, section 2.4.1) --------------------------------------
-P = 2 ** 256 - 2 ** 32 - 977
-Q = 0xFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFFEBAAEDCE6AF48A03BBFD25E8CD0364141
-G = (0x79BE667EF9DCBBAC55A06295CE870B07029BFCDB2DCE28D959F2815B16F81798,
-     0x483ADA7726A3C4655DA4FBFC0E1108A8FD17B448A68554199C47D08FFB10D4B8)
-
-
-def ec_add(a, b):
-    if a is None:
-        return b
-    if b is None:
-        return a
-    if a[0] == b[0] and (a[1] + b[1]) % P == 0:
-        return None
-    lam = 3 * a[0] * a[0] * pow(2 * a[1], -1, P) if a == b else (b[1] - a[1]) * pow(b[0] - a[0], -1, P)
-    x = (lam * lam - a[0] - b[0]) % P
-    return x, (lam * (a[0] - x) - a[1]) % P
-
-
-def ec_neg(a):
-    return None if a is None else (a[0], -a[1] % P)
-
-
-def ec_mul(k, a):
-    r = None
-    for bit in bin(k % Q)[2:]:
-        r = ec_add(r, r)
-        if bit == "1":
-            r = ec_add(r, a)
-    return r
-
-
-def ec_image(a) -> bytes:
-    """Serializer<EC>: 0x04 | x | y, infinity 0x06 and zeros"""
-    return b"\x06" + bytes(64) if a is None else b"\x04" + a[0].to_bytes(32, "big") + a[1].to_bytes(32, "big")
-
-
-def ec_from_image(b: bytes):
-    assert len(b) == 65 and b[0] in (4, 6)
-    return None if b[0] & 2 else (int.from_bytes(b[1:33], "big"), int.from_bytes(b[33:], "big"))
-
-
-def lagrange(nodes, x):
-    """the basis over `nodes` at x, mod Q"""
-    out = []
-    for i, xi in enumerate(nodes):
-        num = den = 1
-        for j, xj in enumerate(nodes):
-            if i != j:
-                num, den = num * (x - xj) % Q, den * (xi - xj) % Q
-        out.append(num * pow(den, -1, Q) % Q)
-    return out
-
-
-def feldman_verify(share: int, commitments, index: int) -> bool:
-    lam = lagrange(range(len(commitments)), index)
-    v = None
-    for l, c in zip(lam, commitments):
-        v = ec_add(v, ec_mul(l, c))
-    return v == ec_mul(share, G)
-
-
-def golden():
-    with open(GOLDEN) as fh:
-        return json.load(fh)["data"]
-
-
-def run_shares(run):
-    raw = bytes.fromhex(run["shares"])
-    assert len(raw) == 32 * run["n"]
-    return [int.from_bytes(raw[32 * i:32 * i + 32], "big") for i in range(run["n"])]
-
-
-def run_commitments(run):
-    return [ec_from_image(bytes.fromhex(c)) for c in run["commitments"]]
-
-
-def feldman_binary():
-    """tests/cxx/test_feldman_api.cc compiled against the mirror (build() leaves it in place; rebuilt here when stale)"""
-    src, exe = os.path.join(CXX, "test_feldman_api.cc"), os.path.join(CXX, "_build", "test_feldman_api")
-    lib = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd")
-    newest = max(os.path.getmtime(os.path.join(d, f)) for d, _, fs in os.walk(os.path.join(ROOT, "include")) for f in fs)
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(newest, os.path.getmtime(src)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        b = subprocess.run(["g++", "-std=c++20", "-O2", "-Wall", "-Wextra", "-Wno-unknown-pragmas", f"-I{ROOT}/include", "-o", exe, src,
-                            f"-L{lib}", "-lscl_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
-        assert b.returncode == 0, b.stderr[-4000:]
-    return exe
-
-
-def write_cases(path):
-    d = golden()
-    lines = [f"G {d['G']}"]
-    lines += [f"mul {m['k']} {m['P']}" for m in d["multiples"]]
-    for i in d["identities"]:
-        lines.append(" ".join(["id", i["P"], i["Q"], i["P+Q"], i["P+P"], i["2P"], i["P-P"], i["P+inf"], i["-P"], str(int(i["P==Q"]))]))
-    for r in d["runs"]:
-        lines += [f"prg {r['seed']}", f"run {r['secret']} {r['t']} {r['n']} {r['shares']} {','.join(r['commitments'])}"]
-    # "Feldman hom": two sharings off ONE PRG, the second drawn after the first has advanced it (a space in a seed is a '+')
-    assert [r["first_secret"] for r in d["hom_runs"]] == [0, 1] and len({r["seed"] for r in d["hom_runs"]}) == 1
-    lines.append("prg " + d["hom_runs"][0]["seed"].replace(" ", "+"))
-    lines += [f"run {r['secret']} {r['t']} {r['n']} {r['shares']} {','.join(r['commitments'])}" for r in d["hom_runs"]]
-    lines.append(f"hom {','.join(d['hom']['commitments'])}")
-    with open(path, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
-    return len(lines)
+from cxx_support import ROOT, mirror_binary
+from secp256k1_model import G, Q, ec_add, ec_from_image, ec_image, ec_mul, ec_neg, feldman_verify, golden, run_commitments, run_shares
+from secp256k1_model import write_feldman_cases as write_cases
 
 
 def test_model_reproduces_the_reference_fixture():
     """every entry of the fixture through big-integer affine arithmetic: multiples of G, the identities, the commitments and
     the verdicts (the three tampered inputs false)"""
-    d = golden()
+    d = golden("feldman")
     assert ec_image(G).hex() == d["G"]
     ks = [int(m["k"], 16) for m in d["multiples"]]
     assert ks[:10] == [0, 1, 2, 3, 15, 16, 17, 2 ** 64, 2 ** 255, Q - 1] and len(ks) == 18
@@ -161,7 +52,7 @@ def test_cxx_mirror_computes_what_the_reference_computed(tmp_path):
     fixture through math::EC and ss::feldman* of the mirror"""
     cases = str(tmp_path / "cases.txt")
     n = write_cases(cases)
-    r = subprocess.run([feldman_binary(), cases], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([mirror_binary("feldman"), cases], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert f"{n} cases" in r.stdout and " 0 failures" in r.stdout, r.stdout
 

@@ -17,7 +17,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from test_plugin_field_pins import _refl, gf_mul, spec_mul
+from extremes import gf_mul, spec_mul
+from extremes import refl as _refl
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 with open(os.path.join(HERE, "golden", "golden_gf2_128_gmac.json")) as fh:

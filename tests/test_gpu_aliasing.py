@@ -18,7 +18,7 @@ Two kinds of test, both through the raw C ABI into a tests/redzone.py arena with
   (EC_N = 1, 63, 64, 65 for points), both one-limb phases, and on the kernel paths the knobs of fuzz_abi.KNOBS reach -- for INV /
   DIV the chain lengths "inv_batch" -1 | 8 | 128 and the two-level form "inv_two_level" 4 | 8 at one tile and one tile plus one
   element.  Expected values: oracle_lib.Port for the field, ring and sharing calls; for the secp256k1 family the same entry point
-  out of place (as test_gpu_redzones argues) with the two end lanes against the big-integer model of tests/test_feldman_host.py.
+  out of place (as test_gpu_redzones argues) with the two end lanes against the big-integer model of tests/secp256k1_model.py.
   The aliased window is `inout`, so arena.check() still holds everything else to its pattern.
 * refusals: for every refused pair the exact alias, the output one element into the input and, where the input has rows, the
   output one row into it -- and for every PERMITTED pair the two near misses.  Each returns SCL_ERR_BAD_ARG, names both operands,
@@ -678,7 +678,7 @@ def images(env, pts):
 
 
 def model_ew(op, p, q):
-    import test_feldman_host as F
+    import secp256k1_model as F
     return {O.ADD: lambda: F.ec_add(p, q), O.SUB: lambda: F.ec_add(p, F.ec_neg(q)), O.NEG: lambda: F.ec_neg(p),
             EC_DBL: lambda: F.ec_add(p, p)}[op]()
 
@@ -690,8 +690,8 @@ EC_EW_SPECS = [(name + "-" + alias, op, alias) for name, op in (("add", O.ADD), 
 @pytest.mark.parametrize("label,op,alias", EC_EW_SPECS, ids=[s[0] for s in EC_EW_SPECS])
 def test_ec_ew_in_place(env, label, op, alias):
     """byte-equal to the same entry point out of place (the kernels are deterministic), and the first and the last lane equal to
-    the big-integer model of tests/test_feldman_host.py through their wire images"""
-    import test_feldman_host as F
+    the big-integer model of tests/secp256k1_model.py through their wire images"""
+    import secp256k1_model as F
     binary = op in (O.ADD, O.SUB)
     for n, k in ec_shapes():
         note = f"ec_ew op {op} {alias} n={n} phase {ec_phase(k)}"
@@ -724,8 +724,8 @@ def test_ec_ew_in_place(env, label, op, alias):
 
 def test_ec_mul_in_place(env):
     """dst == points: the lane's table in scratch is built from its point before the point is overwritten"""
-    import test_feldman_host as F
-    from test_gpu_feldman import scalars_host
+    import secp256k1_model as F
+    from gpu_support import scalars_host
     for n, k in ec_shapes():
         note = f"ec_mul dst == points n={n} phase {ec_phase(k)}"
         pts, s = points(env, n, b"al-ml"), scalars(env, n, b"al-ml-s")

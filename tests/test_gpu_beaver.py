@@ -18,6 +18,9 @@ import torch
 
 import extremes as X
 import oracle_lib as O
+from cxx_support import mirror_binary
+from gpu_support import BEAVER_N, BEAVER_ROWS, fname, gpu_env, host, rnd
+from gpu_support import beaver_reference as reference
 
 pytestmark = pytest.mark.gpu
 
@@ -27,57 +30,12 @@ PRIME_FIELDS = [O.M61, O.M127, O.MONT128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 NS = [1, 63, 64, 65, 255, 4099]
 ROWS = [1, 3]
 NMAX, RMAX = max(NS), max(ROWS)
-
-
-def fname(f):
-    return {O.M61: "m61", O.M127: "m127", O.MONT128: "mont128", O.GF2_128: "gf128", O.SECP256K1_SCALAR: "secp_scalar",
-            O.SECP256K1_FIELD: "secp_field"}.get(f, "z2k%d" % (f - 0x100))
+assert (RMAX, NMAX) == (BEAVER_ROWS, BEAVER_N)          # the shape of the shared reference (tests/gpu_support.py)
 
 
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.mpc as mpc
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, mpc, port
-
-
-def rnd(port, f, n, tag: bytes):
-    """n uniform elements from the oracle's own read of PRG bytes"""
-    if O.is_ring(f):
-        bs = O.byte_size(f)
-        return port.from_bytes(f, port.prg(b"beaver-" + tag, [max(n, 1) * bs]))[:n]
-    return port.vector_random(f, b"beaver-" + tag, n)
-
-
-def oracle_finish(port, f, e, d, a, b, c, add_ed):
-    """e b + d a + c (+ e d), one oracle element-wise call per operation; a, b, c [n][L] and e, d [n][L]"""
-    z = port.ew(f, O.ADD, port.ew(f, O.ADD, port.ew(f, O.MUL, e, b), port.ew(f, O.MUL, d, a)), c)
-    return port.ew(f, O.ADD, z, port.ew(f, O.MUL, e, d)) if add_ed else z
-
-
-_REF = {}
-
-
-def reference(port, f):
-    """operands [RMAX][NMAX][L], e, d [NMAX][L] and the oracle's results, once per field"""
-    if f not in _REF:
-        L = O.LIMBS[f]
-        r = {k: rnd(port, f, RMAX * NMAX, k.encode()).reshape(RMAX, NMAX, L) for k in ("x", "y", "a", "b", "c")}
-        r["e"], r["d"] = rnd(port, f, NMAX, b"e"), rnd(port, f, NMAX, b"d")
-        flat = lambda k: r[k].reshape(RMAX * NMAX, L)
-        r["mask_e"] = port.ew(f, O.SUB, flat("x"), flat("a")).reshape(RMAX, NMAX, L)
-        r["mask_d"] = port.ew(f, O.SUB, flat("y"), flat("b")).reshape(RMAX, NMAX, L)
-        tile = lambda k: np.ascontiguousarray(np.broadcast_to(r[k], (RMAX, NMAX, L))).reshape(RMAX * NMAX, L)
-        for add_ed in (0, 1):
-            r["z%d" % add_ed] = oracle_finish(port, f, tile("e"), tile("d"), flat("a"), flat("b"), flat("c"), add_ed).reshape(
-                RMAX, NMAX, L)
-        _REF[f] = r
-    return _REF[f]
+    return gpu_env("mpc")
 
 
 def place(arr, stride, phase_words=0, fill=True):
@@ -89,10 +47,6 @@ def place(arr, stride, phase_words=0, fill=True):
     if fill:
         v.copy_(torch.from_numpy(np.ascontiguousarray(arr).view(np.int64)).cuda())
     return v
-
-
-def host(t):
-    return t.detach().cpu().numpy().view(np.uint64)
 
 
 def layouts(f, N):
@@ -312,6 +266,5 @@ def test_wrapper_refuses_what_the_header_refuses(env):
 def test_cxx_round_trips(env):
     """tests/cxx/test_beaver_api.cc: hip::beaverMask / beaverFinish over Secp256k1Scalar and Mersenne61 (Shamir) and the
     reference's two-party additive shape (party 0 adds e d)"""
-    from test_beaver_host import beaver_binary
-    r = subprocess.run(["timeout", "-k", "10", "120", beaver_binary()], capture_output=True, text=True)
+    r = subprocess.run(["timeout", "-k", "10", "120", mirror_binary("beaver")], capture_output=True, text=True)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout + r.stderr

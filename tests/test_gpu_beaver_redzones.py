@@ -7,60 +7,22 @@ rows in {1, 3} (the mask's output twice as many) at a pitch larger than N, so th
 windows start 0 and 8 bytes past a 16-byte boundary with even and odd pitches (phase 0 with an even pitch is the two-per-lane
 body with its one-element tail at odd N; everything else the one-per-lane form); wider ones 0, 16 and 48 bytes past a 128-byte
 line.  N in {1, 2, 3, 64, 257}: one element, one pair, a pair and a tail, a wavefront, a block and one.  Each case asserts the
-return code, arena.check() and the values (the oracle's, shared with tests/test_gpu_beaver.py).
+return code, arena.check() and the values (the oracle's: beaver_reference of tests/gpu_support.py, shared with tests/test_gpu_beaver.py).
 
 TABLE has one row per entry point; test_every_device_entry_point_has_a_row reads the header and fails when a prototype that
 takes a `_dev` pointer has none."""
-import os
-import re
-
 import numpy as np
 import pytest
-import torch
 
 import oracle_lib as O
 import redzone as R
-from test_gpu_beaver import fname, reference
+from abi_support import MPC, device_entry_points
+from gpu_support import beaver_reference as reference
+from gpu_support import el, fname, gpu_env, mat, placements, settle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD, O.Z2K(62), O.Z2K(128)]
 NS = [1, 2, 3, 64, 257]
 ROWS = [1, 3]
-OK = 0
-
-
-def limbs(f):
-    return O.LIMBS[f]
-
-
-def esz(f):
-    return 8 * limbs(f)
-
-
-def placements(f, N, k):
-    """(align, phase in bytes, pitch in elements): one limb -- both phases, the pitch even and odd in turn; wider -- two of the
-    three phases in rotation at a pitch of N + 3"""
-    if limbs(f) == 1:
-        even = N + 2 + (N % 2)
-        return [(16, 0, even), (16, 0, even + 1), (16, 8, even), (16, 8, even + 1)]
-    return [(128, (0, 16, 48)[(k + i) % 3], N + 3) for i in (0, 1)]
-
-
-def mat(A, name, f, rows, N, pitch, align, phase, kind, data=None):
-    w = A.window(name, N * esz(f), align, phase, rows=rows, pitch_bytes=pitch * esz(f), kind=kind)
-    return w.load(data) if data is not None else w
-
-
-def el(w, f):
-    return w.read(np.uint64).reshape(w.rows, -1, limbs(f))
-
-
-def settle(lib, A, rc, note):
-    assert rc == OK, f"{note}: status {rc} ({lib.scl_mpc_last_error().decode()})"
-    try:
-        A.check()
-    except R.RedZoneError as e:
-        raise R.RedZoneError(f"{note}\n{e}", e.strays, e.count) from None
 
 
 def run_mask(env, f):
@@ -74,7 +36,7 @@ def run_mask(env, f):
                 wx, wy, wa, wb = [mat(A, nm, f, rows, N, pitch, align, phase, "in", r[nm][:rows, :N]) for nm in ("x", "y", "a", "b")]
                 wo = mat(A, "de", f, 2 * rows, N, pitch, align, phase, "out")
                 rc = mpc.lib.scl_mpc_beaver_mask(f, wo.ptr, pitch, wx.ptr, wy.ptr, wa.ptr, wb.ptr, pitch, rows, N, None)
-                settle(mpc.lib, A, rc, note)
+                settle(mpc.lib.scl_mpc_last_error, A, rc, note)
                 got = el(wo, f)
                 assert np.array_equal(got[:rows], r["mask_e"][:rows, :N]) and np.array_equal(got[rows:], r["mask_d"][:rows, :N]), note
 
@@ -95,7 +57,7 @@ def run_finish(env, f):
                 wz = ops[inplace] if inplace else mat(A, "z", f, rows, N, pitch, align, phase, "out")
                 rc = mpc.lib.scl_mpc_beaver_finish(f, wz.ptr, pitch, we.ptr, wd.ptr, ops["a"].ptr, ops["b"].ptr, ops["c"].ptr, pitch, rows,
                                                    ed_rows, N, None)
-                settle(mpc.lib, A, rc, note)
+                settle(mpc.lib.scl_mpc_last_error, A, rc, note)
                 want = np.concatenate([r["z1"][:ed_rows, :N], r["z0"][ed_rows:rows, :N]])
                 assert np.array_equal(el(wz, f), want), note
 
@@ -104,27 +66,14 @@ TABLE = {"scl_mpc_beaver_mask": run_mask, "scl_mpc_beaver_finish": run_finish}
 CASES = [(entry, f) for entry in TABLE for f in FIELDS]
 
 
-def device_entry_points():
-    """the scl_mpc_* prototypes of the header that take a `_dev` pointer"""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip_mpc.h")).read(), flags=re.S)
-    return sorted(m.group(1) for m in re.finditer(r"\b(scl_mpc_\w+)\s*\(([^;{]*?)\)\s*;", src) if re.search(r"\*\s*\w+_dev\b", m.group(2)))
-
-
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.mpc as mpc
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, mpc, port
+    return gpu_env("mpc")
 
 
 def test_every_device_entry_point_has_a_row():
     """(reads the header and the table: needs no GPU)"""
-    names = device_entry_points()
+    names = device_entry_points(MPC)
     assert len(names) >= 2 and sorted(TABLE) == names, sorted(set(TABLE) ^ set(names))
     assert all(any(e == n for e, _ in CASES) for n in names)
 

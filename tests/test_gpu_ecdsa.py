@@ -1,5 +1,5 @@
 """Batched ECDSA over secp256k1 on the GPU: scl_hip_ec_mul and scl_hip_ecdsa_* (csrc/ecdsa_unit.hip) against what the reference
-computed (tests/golden/golden_ecdsa.json) and against the big-integer Python model of tests/test_ecdsa_host.py (itself pinned to
+computed (tests/golden/golden_ecdsa.json) and against the big-integer Python model of tests/secp256k1_model.py (pinned by tests/test_ecdsa_host.py to
 that fixture) -- never against the library.  Everything is exact: every comparison is byte equality of wire images, of scalar
 images or of verdict bytes.  The model's work is kept to a few hundred scalar multiplications over the whole file."""
 import ctypes as C
@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 import torch
 
-from test_ecdsa_host import (conversion, digest_row, ecdsa_binary, ecdsa_sign, ecdsa_verify, golden, sig_from_image, write_cases)
-from test_feldman_host import G, P, Q, ec_from_image, ec_image, ec_mul
+from cxx_support import mirror_binary
+from gpu_support import images, limbs_of, points_dev, rescale, scalars_dev
+from secp256k1_model import G, P, Q, conversion, digest_row, ec_from_image, ec_image, ec_mul, ecdsa_sign, ecdsa_verify, golden, sig_from_image
+from secp256k1_model import write_ecdsa_cases as write_cases
 
 pytestmark = pytest.mark.gpu
 R = 1 << 256
@@ -30,15 +32,6 @@ def scl():
 @pytest.fixture(scope="module")
 def gtable(scl):
     return scl.ec_base_table()
-
-
-def limbs_of(v: int):
-    return [(v >> (64 * i)) & (2 ** 64 - 1) for i in range(4)]
-
-
-def scalars_dev(scl, values) -> torch.Tensor:
-    """integers -> SECP256K1_SCALAR elements (Montgomery limbs) on the device"""
-    return scl.to_device(np.array([limbs_of(v % Q * R % Q) for v in values], dtype=np.uint64).reshape(len(values), 4))
 
 
 def scalar_images(scl, t: torch.Tensor):
@@ -61,28 +54,6 @@ def digests_dev(rows) -> torch.Tensor:
     return torch.from_numpy(np.frombuffer(b"".join(digest_row(d) for d in rows), dtype=np.uint8).copy().reshape(len(rows), 32)).cuda()
 
 
-def points_dev(scl, pts) -> torch.Tensor:
-    """model points -> device points (Z = 1, or infinity), through their images"""
-    raw = torch.from_numpy(np.frombuffer(b"".join(ec_image(p) for p in pts), dtype=np.uint8).copy().reshape(len(pts), 65)).cuda()
-    out, status = scl.ec_wire_unpack(raw)
-    assert not status.any()
-    return out
-
-
-def images(scl, points: torch.Tensor):
-    raw = scl.ec_wire_pack(points.reshape(-1, 12)).cpu().numpy()
-    return [raw[i].tobytes() for i in range(raw.shape[0])]
-
-
-def rescale(scl, points: torch.Tensor, seed: int) -> torch.Tensor:
-    """(X, Y, Z) -> (zX, zY, zZ) with a random non-zero z per point: the same points under other coordinates"""
-    n = points.shape[0]
-    rng = np.random.default_rng(seed)
-    z = [int.from_bytes(rng.bytes(32), "big") % (P - 1) + 1 for _ in range(n)]
-    zl = np.array([limbs_of(v * R % P) for v in z for _ in range(3)], dtype=np.uint64).reshape(3 * n, 4)
-    return scl.ew(scl.SECP256K1_FIELD, scl.MUL, points.reshape(3 * n, 4).contiguous(), scl.to_device(zl)).reshape(n, 12)
-
-
 def raw_points(scl, coords) -> torch.Tensor:
     """(X, Y, Z) plain integers -> device points, on the curve or not"""
     return scl.to_device(np.array([limbs_of(c % P * R % P) for xyz in coords for c in xyz], dtype=np.uint64).reshape(len(coords), 12))
@@ -97,7 +68,7 @@ def tile(items, n):
 def mul_cases():
     """(P, k, image of k P): the fixture's -- four points, infinity among them, seventeen scalars --, then by the model digits 0
     and 15 in windows 0, 1 and 63 of a scalar that is all ones elsewhere"""
-    d = golden()
+    d = golden("ecdsa")
     ks = [int(k, 16) for k in d["scalars"]]
     cases = [(ec_from_image(bytes.fromhex(m["P"])), k, bytes.fromhex(kp)) for m in d["mul"] for k, kp in zip(ks, m["kP"])]
     p = cases[17][0]
@@ -111,7 +82,7 @@ def mul_cases():
 @pytest.fixture(scope="module")
 def sign_cases():
     """the fixture's fourteen signatures: (sk, nonce, digest, signature image)"""
-    d = golden()
+    d = golden("ecdsa")
     s = d["sign"]
     out = [(int(s["sk"], 16), int(s["nonce_message"], 16), bytes.fromhex(s["digest_message"]), bytes.fromhex(s["sig_message"])),
            (int(s["sk"], 16), int(s["nonce_small"], 16), bytes.fromhex(s["digest_small"]), bytes.fromhex(s["sig_small"]))]
@@ -124,7 +95,7 @@ def verify_cases():
     """(pk, (r, s), digest, verdict): the fixture's honest and tampered lanes in the order honest, r + 1, s + 1, other digest,
     other key -- so that accepted and rejected lanes alternate --, the reference's three, and by the model: s = 0 (2), r = 0,
     the forgery whose R is infinity, and u1 G == u2 Q (the addition is a doubling) both accepted and rejected"""
-    d = golden()
+    d = golden("ecdsa")
     out = []
     for g in d["signatures"]:
         pk, other_pk = ec_from_image(bytes.fromhex(g["pk"])), ec_from_image(bytes.fromhex(g["other_pk"]))
@@ -140,7 +111,7 @@ def verify_cases():
 @functools.lru_cache(maxsize=None)
 def one_signer_cases():
     """lanes of ONE key (the reference's "ECDSA sign" key): its three verdicts and the model's special cases"""
-    s = golden()["sign"]
+    s = golden("ecdsa")["sign"]
     sk, pk = int(s["sk"], 16), ec_from_image(bytes.fromhex(s["pk"]))
     dm, ds = bytes.fromhex(s["digest_message"]), bytes.fromhex(s["digest_small"])
     r, sg = sig_from_image(s["sig_message"])
@@ -198,7 +169,7 @@ def test_mul_random_pairs_in_place(scl, gtable):
 def test_conversion(scl):
     """the fixture's conversionFunc(R); off-curve coordinates with X = q + 5 -> 5, flat and under a non-unit Z (x >= q comes
     from no signature); X = p - 1 -> p - 1 - q; infinity -> 0"""
-    sigs = golden()["signatures"]
+    sigs = golden("ecdsa")["signatures"]
     pts = points_dev(scl, [ec_from_image(bytes.fromhex(g["R"])) for g in sigs] + [None])
     want = [bytes.fromhex(g["conversion"]) for g in sigs] + [bytes(32)]
     assert scalar_images(scl, scl.ecdsa_conversion(pts)) == want
@@ -341,7 +312,7 @@ def test_cxx_batch_forms_agree_with_the_per_signature_forms(scl, tmp_path):
     a zero nonce included"""
     cases = str(tmp_path / "cases.txt")
     n = write_cases(cases)
-    r = subprocess.run(["timeout", "-k", "10", "300", ecdsa_binary(), cases, "--device"], capture_output=True, text=True)
+    r = subprocess.run(["timeout", "-k", "10", "300", mirror_binary("ecdsa"), cases, "--device"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "device: 65 signatures" in r.stdout and f"{n} cases" in r.stdout and " 0 failures" in r.stdout, r.stdout
 

@@ -1,6 +1,6 @@
 """secp256k1 group arithmetic and Feldman VSS on the GPU: scl_hip_ec_* and scl_hip_feldman_* (csrc/ec_unit.hip) against what the
-reference computed (tests/golden/golden_feldman.json) and against the big-integer Python model of tests/test_feldman_host.py
-(itself pinned to that fixture) -- never against the library.  Everything is exact: every comparison is byte equality of wire
+reference computed (tests/golden/golden_feldman.json) and against the big-integer Python model of tests/secp256k1_model.py
+(pinned to that fixture by tests/test_feldman_host.py) -- never against the library.  Everything is exact: every comparison is byte equality of wire
 images or of verdict bytes.  The model's work is kept under ~600 scalar multiplications over the whole file."""
 import ctypes as C
 import subprocess
@@ -9,12 +9,13 @@ import numpy as np
 import pytest
 import torch
 
-from test_feldman_host import (G, Q, feldman_binary, write_cases, ec_add, ec_from_image, ec_image, ec_mul, ec_neg, feldman_verify, golden, run_commitments,
-                               run_shares)
+from cxx_support import mirror_binary
+from gpu_support import images, points_dev, rescale, scalars_dev, scalars_host
+from secp256k1_model import G, Q, ec_add, ec_from_image, ec_image, ec_mul, ec_neg, feldman_verify, golden, run_shares
+from secp256k1_model import write_feldman_cases as write_cases
 
 pytestmark = pytest.mark.gpu
 R = 1 << 256
-P = 2 ** 256 - 2 ** 32 - 977
 COUNTS = [1, 63, 64, 65, 300]
 
 
@@ -30,47 +31,9 @@ def gtable(scl):
     return scl.ec_base_table()
 
 
-def limbs_of(v: int):
-    return [(v >> (64 * i)) & (2 ** 64 - 1) for i in range(4)]
-
-
-def scalars_dev(scl, values) -> torch.Tensor:
-    """integers -> SECP256K1_SCALAR elements (Montgomery limbs) on the device"""
-    return scl.to_device(np.array([limbs_of(v % Q * R % Q) for v in values], dtype=np.uint64).reshape(len(values), 4))
-
-
-def scalars_host(scl, t: torch.Tensor):
-    """SECP256K1_SCALAR elements -> integers"""
-    rinv = pow(R, -1, Q)
-    return [sum(int(w) << (64 * i) for i, w in enumerate(row)) * rinv % Q for row in scl.to_host(t).reshape(-1, 4)]
-
-
-def points_dev(scl, pts) -> torch.Tensor:
-    """model points -> device points (Z = 1, or infinity), through their images"""
-    raw = torch.from_numpy(np.frombuffer(b"".join(ec_image(p) for p in pts), dtype=np.uint8).copy().reshape(len(pts), 65)).cuda()
-    out, status = scl.ec_wire_unpack(raw)
-    assert not status.any()
-    return out
-
-
-def images(scl, points: torch.Tensor):
-    raw = scl.ec_wire_pack(points.reshape(-1, 12)).cpu().numpy()
-    return [raw[i].tobytes() for i in range(raw.shape[0])]
-
-
-def rescale(scl, points: torch.Tensor, seed: int) -> torch.Tensor:
-    """(X, Y, Z) -> (zX, zY, zZ) with a random non-zero z per point: the same points under other coordinates"""
-    n = points.shape[0]
-    rng = np.random.default_rng(seed)
-    z = [int.from_bytes(rng.bytes(32), "big") % (P - 1) + 1 for _ in range(n)]
-    zl = np.array([limbs_of(v * R % P) for v in z for _ in range(3)], dtype=np.uint64).reshape(3 * n, 4)
-    f = scl.SECP256K1_FIELD
-    return scl.ew(f, scl.MUL, points.reshape(3 * n, 4).contiguous(), scl.to_device(zl)).reshape(n, 12)
-
-
 def fixed_scalars():
     """the fixture's scalars with their reference-computed multiples, and one non-zero window at either end (model)"""
-    d = golden()
+    d = golden("feldman")
     ks = [int(m["k"], 16) for m in d["multiples"]]
     want = [bytes.fromhex(m["P"]) for m in d["multiples"]]
     for w in (0, 1, 63):
@@ -113,7 +76,7 @@ def test_mul_base_random_scalars(scl, gtable):
 def test_elementwise_and_equality_on_the_fixture_identities(scl):
     """every identity of the fixture at n = 65 (tiled): P + Q, P + P through ADD, 2P, P - P = infinity, infinity as either
     operand, -P; operands under random projective coordinates; equality under rescaling; in place (dst == a)"""
-    ids = golden()["identities"]
+    ids = golden("feldman")["identities"]
     n = 65
     pick = [ids[i % len(ids)] for i in range(n)]
     col = lambda key: [bytes.fromhex(c[key]) for c in pick]
@@ -187,7 +150,7 @@ def test_cxx_batch_forms_agree_with_the_per_secret_forms(scl, tmp_path):
     summed sharings) equal those of ss::feldmanSecretShare / feldmanVerify secret by secret"""
     cases = str(tmp_path / "cases.txt")
     n = write_cases(cases)
-    r = subprocess.run(["timeout", "-k", "10", "300", feldman_binary(), cases, "--device"], capture_output=True, text=True)
+    r = subprocess.run(["timeout", "-k", "10", "300", mirror_binary("feldman"), cases, "--device"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "device: 65 secrets" in r.stdout and f"{n} cases" in r.stdout and " 0 failures" in r.stdout, r.stdout
 
@@ -216,7 +179,7 @@ def test_feldman_commit_and_verify_reproduce_the_reference(scl, gtable, which):
     one PRG -- through scl_hip_shamir_share_prg over the scalar field: shares and commitments equal the reference's byte for
     byte, every party verifies, index 0 verifies the secret, the three tampered inputs give 0"""
     f = scl.SECP256K1_SCALAR
-    for r in golden()[which]:
+    for r in golden("feldman")[which]:
         t, n = r["t"], r["n"]
         secrets = scalars_dev(scl, [r["secret"]])
         shares = scl.shamir_share_prg(f, secrets, t, n, r["seed"].encode(), first_secret=r["first_secret"])

@@ -1,5 +1,5 @@
-"""Honest-majority multiplication on the GPU (scl_amd.hm over libscl_hip_hm.so) against the Python model of tests/test_hm_host.py,
-which that file pins to what the reference produced: device output equals the model byte for byte.  Each test's docstring names
+"""Honest-majority multiplication on the GPU (scl_amd.hm over libscl_hip_hm.so) against the Python model of tests/port_models.py,
+which tests/test_hm_host.py pins to what the reference produced: device output equals the model byte for byte.  Each test's docstring names
 its shapes.  One model run per (field, shape) at the largest N; every smaller N is a prefix of it."""
 import ctypes as C
 import subprocess
@@ -9,9 +9,13 @@ import pytest
 import torch
 
 import oracle_lib as O
-from test_gpu_beaver import fname, host, rnd
-from test_hm_host import (TAGS, double_blocks, golden, hm_binary, model_apply, model_double, model_finish, model_him, model_inputs, model_mask,
-                          model_open, protocol_entry)
+from cxx_support import mirror_binary
+from gpu_support import HM_N, deal_all, fname, gpu_env, host, pm1, pool, rnd
+from gpu_support import HM_SEED as SEED
+from gpu_support import hm_chain_buffers as chain_buffers
+from gpu_support import hm_reference as reference
+from port_models import TAGS, double_blocks, golden, model_apply, model_double, model_finish, model_him, model_inputs, model_mask, model_open
+from port_models import hm_protocol_entry as protocol_entry
 
 pytestmark = pytest.mark.gpu
 
@@ -19,33 +23,15 @@ FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_F
 FUSED_FIELDS = [O.M61, O.M127, O.GF2_128]
 NS = [1, 2, 3, 64, 257, 1025]
 NMAX = max(NS)
+assert NMAX == HM_N          # the shape of the shared reference (tests/gpu_support.py)
 DOUBLE_NT = [(3, 1), (4, 1), (7, 3), (10, 3), (9, 4)]
 APPLY_MN = [(1, 1), (3, 4), (7, 10), (17, 20), (40, 41), (5, 16), (5, 17), (43, 12), (90, 12)]
 APPLY_NS = [1, 3, 64, 257, 1025]
-SEED = b"gpu hm"
 
 
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.hm as hm
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, hm, port
-
-
-_REF = {}
-
-
-def reference(port, f, n, t, counter0=0, N=NMAX):
-    """the model's lo, hi [n][N][L] and r [N][L], once per case"""
-    key = (f, n, t, counter0, N)
-    if key not in _REF:
-        _REF[key] = model_double(port, f, SEED, counter0, N, t, n)
-    return _REF[key]
+    return gpu_env("hm")
 
 
 def same(got, want, N, note):
@@ -58,19 +44,6 @@ def expect_scratch(hm, f, N, n, t, flags=0):
     fused = f in FUSED_FIELDS and t <= 3 and not flags
     assert need == (0 if fused else (1 + 3 * t) * N * 8 * O.LIMBS[f]), (fname(f), N, n, t, flags)
     return fused
-
-
-def pm1(port, f):
-    """p - 1 (GF(2^128): all ones), the largest canonical element"""
-    if f == O.GF2_128:
-        return np.full(2, 2 ** 64 - 1, dtype=np.uint64)
-    return port.ew(f, O.SUB, port.from_int(f, 0)[None], port.from_int(f, 1)[None])[0]
-
-
-def pool(port, f, count, tag):
-    """`count` elements that repeat a uniform pool of 4099 with an odd period (rows and batches all differ)"""
-    base = rnd(port, f, 4099, tag)
-    return base[np.arange(count) % 4099]
 
 
 # ---- double sharings -------------------------------------------------------------------------------------------------------------
@@ -300,17 +273,11 @@ def test_finish_equals_the_model(env, f):
 
 
 # ---- the protocol ------------------------------------------------------------------------------------------------------------
-def deal_all(hm, f, S, t, n, seeds, lo, hi, scratch=None, flags=0):
-    """dealer i's S double sharings into lo[i], hi[i]: [dealer][party][S][L]"""
-    for i, s in enumerate(seeds):
-        hm.double_share(f, S, t, n, s, out=(lo[i], hi[i]), scratch=scratch, flags=flags)
-
-
 def test_the_fixtures_protocol_end_to_end_on_the_device(env):
     """n dealers with the fixture's seeds -> the extraction at both degrees, every party in one launch -> mask -> finish ->
     shamir_recover: every intermediate equals what the reference computed"""
     scl, hm, port = env
-    for e in golden()["protocol"]:
+    for e in golden("hm")["protocol"]:
         f, n, t = TAGS[e["field"]], e["n"], e["t"]
         want, S = protocol_entry(port, f, e)
         L, m = O.LIMBS[f], n - t
@@ -338,12 +305,6 @@ def pitched(t, width):
     buf = torch.zeros(rows, width, L, dtype=torch.int64, device=t.device)
     buf[:, :P] = t
     return buf[:, :P]
-
-
-def chain_buffers(f, n, t, S):
-    L, m = O.LIMBS[f], n - t
-    z = lambda *shape: torch.zeros(*shape, L, dtype=torch.int64, device="cuda")
-    return {"lo": z(n, n, S), "hi": z(n, n, S), "R_lo": z(n, m, S), "R_hi": z(n, m, S), "d": z(n, m * S), "z": z(n, m * S), "out": z(m * S)}
 
 
 def run_chain(scl, hm, f, n, t, S, P, seeds, Md, xs, ys, lam, B, scratch=None, flags=0):
@@ -449,5 +410,5 @@ def test_wrapper_refuses_what_the_header_refuses(env):
 def test_cxx_round_trips(env):
     """tests/cxx/test_hm_api.cc --gpu: hip::dealDoubleSharings equals ss::doubleShare on one PRG, and deal, hip::applyMatrix,
     hip::mulMask, hip::mulFinish, recover multiplies"""
-    r = subprocess.run([hm_binary(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([mirror_binary("hm"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -11,59 +11,19 @@ N in {1, 2, 3, 64, 257}.  Each case asserts the return code, arena.check() and t
 
 TABLE has one row per entry point; test_every_device_entry_point_has_a_row reads the header and fails when a prototype that takes
 a `_dev` pointer has none."""
-import os
-import re
-
 import numpy as np
 import pytest
-import torch
 
 import oracle_lib as O
 import redzone as R
-from test_gpu_beaver import fname
-from test_gpu_hm import SEED, pool, reference
-from test_hm_host import model_apply, model_finish, model_him, model_mask, model_open
+from abi_support import HM, device_entry_points
+from gpu_support import HM_SEED as SEED
+from gpu_support import hm_reference as reference
+from gpu_support import el, esz, fname, gpu_env, limbs, mat, placements, pool, settle
+from port_models import model_apply, model_finish, model_him, model_mask, model_open
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 NS = [1, 2, 3, 64, 257]
-OK = 0
-
-
-def limbs(f):
-    return O.LIMBS[f]
-
-
-def esz(f):
-    return 8 * limbs(f)
-
-
-def placements(f, N, k):
-    """(align, phase in bytes, pitch in elements): one limb -- both phases, the pitch even and odd in turn; wider -- two of the
-    three phases in rotation at a pitch of N + 3"""
-    if limbs(f) == 1:
-        even = N + 2 + (N % 2)
-        return [(16, 0, even), (16, 0, even + 1), (16, 8, even), (16, 8, even + 1)]
-    return [(128, (0, 16, 48)[(k + i) % 3], N + 3) for i in (0, 1)]
-
-
-def mat(A, name, f, rows, N, pitch, align, phase, kind="out", data=None):
-    w = A.window(name, N * esz(f), align, phase, rows=rows, pitch_bytes=pitch * esz(f), kind=kind)
-    if data is not None:
-        w.load(np.ascontiguousarray(data))
-    return w
-
-
-def el(w, f):
-    return w.read(np.uint64).reshape(w.rows, -1, limbs(f))
-
-
-def settle(lib, A, rc, note):
-    assert rc == OK, f"{note}: status {rc} ({lib.scl_hm_last_error().decode()})"
-    try:
-        A.check()
-    except R.RedZoneError as e:
-        raise R.RedZoneError(f"{note}\n{e}", e.strays, e.count) from None
 
 
 def run_double(env, f):
@@ -81,7 +41,7 @@ def run_double(env, f):
                 assert (need == 0) == (f in (O.M61, O.M127, O.GF2_128) and t <= 3 and not flags), note
                 ws = A.window("scratch", need, 16, 0, kind="out") if need else None
                 rc = hm.lib.scl_hm_double_share_prg(f, wl.ptr, wh.ptr, pitch, N, t, n, SEED, len(SEED), 0, ws.ptr if ws else None, flags, None)
-                settle(hm.lib, A, rc, note)
+                settle(hm.lib.scl_hm_last_error, A, rc, note)
                 for w, m, nm in zip((wl, wh), want, ("lo", "hi")):
                     assert np.array_equal(el(w, f), m[:, :N]), f"{note}: {nm}"
 
@@ -106,7 +66,7 @@ def run_apply(env, f):
                     obs = (wo[1].ptr - wo[0].ptr) // esz(f) if batch > 1 else 0
                     assert batch == 1 or ((wi[1].ptr - wi[0].ptr) % esz(f) == 0 and (wo[1].ptr - wo[0].ptr) % esz(f) == 0)
                     rc = hm.lib.scl_hm_apply(f, wo[0].ptr, pitch, obs, wi[0].ptr, pitch, ibs, wm.ptr, n + 1, m, n, batch, N, None)
-                    settle(hm.lib, A, rc, note)
+                    settle(hm.lib.scl_hm_last_error, A, rc, note)
                     for b in range(batch):
                         assert np.array_equal(el(wo[b], f), model_apply(port, f, M, xs[b])), f"{note}: batch {b}"
 
@@ -126,7 +86,7 @@ def run_mask(env, f):
                     wr = mat(A, "r2", f, rows, N, pitch, align, phase, "inout" if in_place else "in", r2)
                     wd = wr if in_place else mat(A, "d", f, rows, N, pitch + 2, align, phase)
                     rc = hm.lib.scl_hm_mul_mask(f, wd.ptr, pitch if in_place else pitch + 2, wx.ptr, wy.ptr, wr.ptr, pitch, rows, N, None)
-                    settle(hm.lib, A, rc, note)
+                    settle(hm.lib.scl_hm_last_error, A, rc, note)
                     assert np.array_equal(el(wd, f), want), note
 
 
@@ -149,7 +109,7 @@ def run_finish(env, f):
                     wz = wr if in_place else mat(A, "z", f, rows, N, pitch + 2, align, phase)
                     rc = hm.lib.scl_hm_mul_finish(f, wz.ptr, pitch if in_place else pitch + 2, wd.ptr, pitch, lam.ctypes.data, m, wr.ptr, pitch,
                                                   rows, N, None)
-                    settle(hm.lib, A, rc, note)
+                    settle(hm.lib.scl_hm_last_error, A, rc, note)
                     assert np.array_equal(el(wz, f), want), note
 
 
@@ -157,27 +117,14 @@ TABLE = {"scl_hm_double_share_prg": run_double, "scl_hm_apply": run_apply, "scl_
 CASES = [(entry, f) for entry in TABLE for f in FIELDS]
 
 
-def device_entry_points():
-    """the scl_hm_* prototypes of the header that take a `_dev` pointer"""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip_hm.h")).read(), flags=re.S)
-    return sorted(m.group(1) for m in re.finditer(r"\b(scl_hm_\w+)\s*\(([^;{]*?)\)\s*;", src) if re.search(r"\*\s*\w+_dev\b", m.group(2)))
-
-
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.hm as hm
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, hm, port
+    return gpu_env("hm")
 
 
 def test_every_device_entry_point_has_a_row():
     """(reads the header and the table: needs no GPU)"""
-    names = device_entry_points()
+    names = device_entry_points(HM)
     assert len(names) == 4 and sorted(TABLE) == names, sorted(set(TABLE) ^ set(names))
     assert all(any(e == n for e, _ in CASES) for n in names)
 

@@ -1,5 +1,5 @@
 """Inner and matrix products of Shamir sharings at one opening on the GPU (scl_amd.ip over libscl_hip_ip.so) against the Python
-model of tests/test_ip_host.py, which that file pins to what the reference produced: device output equals the model byte for byte.
+model of tests/port_models.py, which tests/test_ip_host.py pins to what the reference produced: device output equals the model byte for byte.
 Each test's docstring names its shapes.  One model run per field at the largest shape -- the sums are prefix sums over the terms
 and every smaller N is a prefix of the columns -- uploaded once; every layout is a device copy of it."""
 import subprocess
@@ -9,9 +9,12 @@ import pytest
 import torch
 
 import oracle_lib as O
-from test_gpu_beaver import fname, host, rnd
-from test_gpu_hm import chain_buffers, deal_all, pm1, pool
-from test_ip_host import TAGS, _ew, golden, inner_entry, ip_binary, matrix_entry, model_dot_mask, model_matmul_mask
+from cxx_support import mirror_binary
+from gpu_support import deal_all, fname, gpu_env, host, only_the_view_was_written, placed, pm1, pool, rnd
+from gpu_support import hm_chain_buffers as chain_buffers
+from port_models import TAGS3 as TAGS
+from port_models import ew as _ew
+from port_models import golden, inner_entry, matrix_entry, model_dot_mask, model_matmul_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -27,37 +30,12 @@ MAT_NS = [1, 3, 64, 257]
 
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.hm as hm
-    import scl_amd.ip as ip
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, hm, ip, port
+    return gpu_env("hm", "ip")
 
 
 def pitches(f, N):
     """row pitches: N, an even one larger than N (Mersenne61: two columns per lane) and an odd one"""
     return [N, N + 2 + (N % 2), N + 3 + (N % 2)]
-
-
-def placed(dense, strides, phase=0):
-    """a device copy of `dense` [d0]..[dk][N][L] whose leading axes lie `strides` elements apart, `phase` elements into a zeroed
-    buffer -> (buffer, view)"""
-    lead, (N, L) = dense.shape[:-2], dense.shape[-2:]
-    extent = sum((n - 1) * s for n, s in zip(lead, strides)) + N
-    buf = torch.zeros((extent + phase + 2) * L, dtype=torch.int64, device="cuda")
-    v = torch.as_strided(buf, tuple(dense.shape), tuple(s * L for s in strides) + (L, 1), phase * L)
-    v.copy_(dense)
-    return buf, v
-
-
-def only_the_view_was_written(buf, view):
-    rest = buf.clone()
-    torch.as_strided(rest, tuple(view.shape), view.stride(), view.storage_offset() - buf.storage_offset()).zero_()
-    return not rest.any().item()
 
 
 _DOT = {}
@@ -243,7 +221,7 @@ def test_the_fixture_end_to_end_on_the_device(env):
     """every entry of golden_ip.json: the shares of x_k and y_k rebuilt by the model -> dot_mask (matmul_mask) -> hm.mul_finish
     -> scl.shamir_recover; every intermediate equals what the reference computed"""
     scl, hm, ip, port = env
-    g = golden()
+    g = golden("ip")
     for e in g["inner"]:
         f = TAGS[e["field"]]
         xs, ys, lo, hi, want = inner_entry(port, f, e)
@@ -426,5 +404,5 @@ def test_wrapper_refuses_what_the_header_refuses(env):
 def test_cxx_round_trips(env):
     """tests/cxx/test_ip_api.cc --gpu, a fresh child process: hip::dotMask and hip::matmulMask equal the per-element form of
     detail/ip.hpp on the host, and share -> dotMask -> hip::mulFinish -> recover is the inner product"""
-    r = subprocess.run([ip_binary(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([mirror_binary("ip"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

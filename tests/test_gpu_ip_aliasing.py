@@ -18,18 +18,15 @@ import re
 
 import numpy as np
 import pytest
-import torch
 
 import oracle_lib as O
 import redzone as R
-from test_gpu_beaver import fname
-from test_gpu_hm import pool
-from test_gpu_hm_redzones import el, esz, limbs, mat, placements
-from test_ip_host import model_dot_mask, model_matmul_mask
+from cxx_support import ROOT
+from gpu_support import el, esz, fname, gpu_env, limbs, mat, placements, pool, settle
+from port_models import model_dot_mask, model_matmul_mask
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
-OK, ERR_BAD_ARG = 0, 3
+ERR_BAD_ARG = 3
 
 _PAIRS = {("d_dev", "x_dev"): ("refuse", "d_dev must not overlap x_dev"), ("d_dev", "y_dev"): ("refuse", "d_dev must not overlap y_dev"),
           ("d_dev", "r2_dev"): ("permit", "d_dev may be r2_dev")}
@@ -94,22 +91,7 @@ def test_each_decision_is_worded_in_the_comment_of_its_entry_point():
 # ---------------------------------------------------------------------------------------------- on the device
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.ip as ip
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, ip, port
-
-
-def settle(lib, A, rc, note):
-    assert rc == OK, f"{note}: status {rc} ({lib.scl_ip_last_error().decode()})"
-    try:
-        A.check()
-    except R.RedZoneError as e:
-        raise R.RedZoneError(f"{note}\n{e}", e.strays, e.count) from None
+    return gpu_env("ip")
 
 
 @pytest.mark.gpu
@@ -133,13 +115,13 @@ def test_the_permitted_alias_and_coinciding_inputs(env, f):
             wy = mat(A, "y", f, terms * rows, N, pitch, align, phase, "in", y.reshape(-1, N, L))
             wr = mat(A, "r2", f, rows, N, pitch, align, phase, "inout", r2)
             rc = ip.lib.scl_ip_dot_mask(f, wr.ptr, pitch, wx.ptr, rows * pitch, wy.ptr, rows * pitch, wr.ptr, pitch, terms, rows, N, None)
-            settle(ip.lib, A, rc, "dot_mask in place " + note)
+            settle(ip.lib.scl_ip_last_error, A, rc, "dot_mask in place " + note)
             assert np.array_equal(el(wr, f), model_dot_mask(port, f, x, y, r2)), "dot_mask in place " + note
             A = R.Arena()
             wx = mat(A, "x", f, terms * rows, N, pitch, align, phase, "in", x.reshape(-1, N, L))
             wd = mat(A, "d", f, rows, N, pitch + 2, align, phase)
             rc = ip.lib.scl_ip_dot_mask(f, wd.ptr, pitch + 2, wx.ptr, rows * pitch, wx.ptr, rows * pitch, wx.ptr, pitch, terms, rows, N, None)
-            settle(ip.lib, A, rc, "dot_mask x == y == r2 " + note)
+            settle(ip.lib.scl_ip_last_error, A, rc, "dot_mask x == y == r2 " + note)
             assert np.array_equal(el(wd, f), model_dot_mask(port, f, x, x, x[0])), "dot_mask x == y == r2 " + note
             A = R.Arena()
             wX = mat(A, "x", f, batch * a * K, N, pitch, align, phase, "in", X.reshape(-1, N, L))
@@ -147,7 +129,7 @@ def test_the_permitted_alias_and_coinciding_inputs(env, f):
             wR = mat(A, "r2", f, batch * a * b, N, pitch, align, phase, "inout", R2.reshape(-1, N, L))
             rc = ip.lib.scl_ip_matmul_mask(f, wR.ptr, pitch, a * b * pitch, wX.ptr, pitch, a * K * pitch, wY.ptr, pitch, K * b * pitch, wR.ptr, pitch,
                                            a * b * pitch, a, K, b, batch, N, None)
-            settle(ip.lib, A, rc, "matmul_mask in place " + note)
+            settle(ip.lib.scl_ip_last_error, A, rc, "matmul_mask in place " + note)
             assert np.array_equal(el(wR, f).reshape(batch, a, b, N, L), model_matmul_mask(port, f, X, Y, R2)), "matmul_mask in place " + note
 
 

@@ -12,32 +12,17 @@ and the values (the model's).
 
 TABLE has one row per entry point; test_every_device_entry_point_has_a_row reads the header and fails when a prototype that takes
 a `_dev` pointer has none."""
-import os
-import re
-
 import numpy as np
 import pytest
-import torch
 
 import oracle_lib as O
 import redzone as R
-from test_gpu_beaver import fname
-from test_gpu_hm import pool
-from test_gpu_hm_redzones import el, esz, limbs, mat, placements
-from test_ip_host import model_dot_mask, model_matmul_mask
+from abi_support import IP, device_entry_points
+from gpu_support import el, esz, fname, gpu_env, limbs, mat, placements, pool, settle
+from port_models import model_dot_mask, model_matmul_mask
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 NS = [1, 2, 3, 64, 257]
-OK = 0
-
-
-def settle(lib, A, rc, note):
-    assert rc == OK, f"{note}: status {rc} ({lib.scl_ip_last_error().decode()})"
-    try:
-        A.check()
-    except R.RedZoneError as e:
-        raise R.RedZoneError(f"{note}\n{e}", e.strays, e.count) from None
 
 
 def stride_between(ws, f):
@@ -74,7 +59,7 @@ def run_dot(env, f):
                     wd = wr if mode == "in place" else mat(A, "d", f, rows, N, pitch + 2, align, phase)
                     rc = ip.lib.scl_ip_dot_mask(f, wd.ptr, pitch if mode == "in place" else pitch + 2, wx[0].ptr, stride_between(wx, f), wy[0].ptr,
                                                 stride_between(wy, f), None if mode == "none" else wr.ptr, pitch, terms, rows, N, None)
-                    settle(ip.lib, A, rc, note)
+                    settle(ip.lib.scl_ip_last_error, A, rc, note)
                     assert np.array_equal(el(wd, f), want[mode != "none"]), note
 
 
@@ -112,7 +97,7 @@ def run_matmul(env, f):
                     rc = ip.lib.scl_ip_matmul_mask(f, wd[0].ptr, dp, stride_between(wd, f), wx[0].ptr, pitch, stride_between(wx, f), wy[0].ptr, pitch,
                                                    stride_between(wy, f), None if mode == "none" else wr[0].ptr, pitch, stride_between(wr, f), a, K, b,
                                                    batch, N, None)
-                    settle(ip.lib, A, rc, note)
+                    settle(ip.lib.scl_ip_last_error, A, rc, note)
                     for q in range(batch):
                         assert np.array_equal(el(wd[q], f).reshape(a, b, N, L), want[mode != "none"][q]), f"{note}: batch {q}"
 
@@ -121,27 +106,14 @@ TABLE = {"scl_ip_dot_mask": run_dot, "scl_ip_matmul_mask": run_matmul}
 CASES = [(entry, f) for entry in TABLE for f in FIELDS]
 
 
-def device_entry_points():
-    """the scl_ip_* prototypes of the header that take a `_dev` pointer"""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip_ip.h")).read(), flags=re.S)
-    return sorted(m.group(1) for m in re.finditer(r"\b(scl_ip_\w+)\s*\(([^;{]*?)\)\s*;", src) if re.search(r"\*\s*\w+_dev\b", m.group(2)))
-
-
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.ip as ip
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, ip, port
+    return gpu_env("ip")
 
 
 def test_every_device_entry_point_has_a_row():
     """(reads the header and the table: needs no GPU)"""
-    names = device_entry_points()
+    names = device_entry_points(IP)
     assert len(names) == 2 and sorted(TABLE) == names, sorted(set(TABLE) ^ set(names))
     assert all(any(e == n for e, _ in CASES) for n in names)
 

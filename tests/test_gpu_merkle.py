@@ -1,16 +1,15 @@
 """Merkle commitments on the GPU: scl_hip_sha256 and scl_hip_merkle_* (csrc/sha256.hpp, hash_unit.hip) against hashlib and the
-Python model of the reference's tree (tests/test_merkle_host.py, itself pinned to trees the reference hashed) -- never
+Python model of the reference's tree (tests/merkle_model.py, pinned to trees the reference hashed by tests/test_merkle_host.py) -- never
 against the library.  Leaf digests of the large trees are random 32-byte strings: the kernels above the leaf level see digests
 only."""
-import hashlib
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
-from test_merkle_host import (ELEMENT_BYTES, golden, golden_leaves, merkle_binary, model_levels, model_path, model_tree_bytes,
-                              sha, write_cases)
+from cxx_support import mirror_binary
+from merkle_model import golden, golden_leaves, model_levels, model_path, model_tree_bytes, sha, write_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -233,7 +232,7 @@ def test_device_and_host_proofs_are_interchangeable(scl, tmp_path):
     device-built proof verifies under the host mirror's MerkleTree::verify and every host-built one under hip::merkleVerify"""
     cases = str(tmp_path / "cases.txt")
     write_cases(cases)
-    r = subprocess.run(["timeout", "-k", "10", "300", merkle_binary(), cases, "--device"], capture_output=True, text=True)
+    r = subprocess.run(["timeout", "-k", "10", "300", mirror_binary("merkle"), cases, "--device"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "(device)" in r.stdout and "24 trees" in r.stdout and " 0 failures" in r.stdout, r.stdout
 

@@ -1,6 +1,6 @@
 """Pedersen VSS on the GPU: scl_hip_ec_mul_two_base, scl_hip_ec_matmul and scl_hip_pedersen_* (csrc/pedersen_unit.hip) against
 what the reference computed (tests/golden/golden_pedersen.json) and against the big-integer Python model of
-tests/test_pedersen_host.py (itself pinned to that fixture) -- never against the library, except where a test says that two
+tests/secp256k1_model.py (pinned to that fixture by tests/test_pedersen_host.py) -- never against the library, except where a test says that two
 entry points must agree.  Everything is exact: every comparison is byte equality of wire images or of verdict bytes.  The
 model's work is kept to a few hundred scalar multiplications over the whole file."""
 import ctypes as C
@@ -11,10 +11,11 @@ import numpy as np
 import pytest
 import torch
 
-from test_feldman_host import G, Q, ec_add, ec_from_image, ec_image, ec_mul
-from test_gpu_feldman import images, points_dev, rescale, scalars_dev, scalars_host
-from test_pedersen_host import (every_run, golden, matrix_of, pedersen_binary, pedersen_commitment, pedersen_verify, run_commitments,
-                                run_pairs, scalar_of, write_cases)
+from cxx_support import mirror_binary
+from gpu_support import images, points_dev, rescale, scalars_dev, scalars_host
+from secp256k1_model import G, Q, ec_from_image, ec_image, ec_mul, matrix_of, pedersen_commitment, pedersen_verify, run_commitments, run_pairs, scalar_of
+from secp256k1_model import pedersen_golden as golden
+from secp256k1_model import write_pedersen_cases as write_cases
 
 pytestmark = pytest.mark.gpu
 INF = b"\x06" + bytes(64)
@@ -293,7 +294,7 @@ def test_cxx_batch_forms_agree_with_the_per_secret_forms(scl, tmp_path):
     fixture's outputs on the fixture's inputs, every output share verifying at its index as in "Pedersen apply\""""
     cases = str(tmp_path / "cases.txt")
     n = write_cases(cases)
-    r = subprocess.run(["timeout", "-k", "10", "300", pedersen_binary(), cases, "--device"], capture_output=True, text=True)
+    r = subprocess.run(["timeout", "-k", "10", "300", mirror_binary("pedersen"), cases, "--device"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "device: 65 secrets" in r.stdout and "device apply: 2 matrices" in r.stdout, r.stdout
     assert f"{n} cases" in r.stdout and " 0 failures" in r.stdout, r.stdout

@@ -7,60 +7,23 @@ n rows at a pitch larger than N, so the gaps between rows are flanks too -- and,
 exactly scl_prep_triples_scratch_bytes.  One-limb windows start 0 and 8 bytes past a 16-byte boundary with even and odd pitches
 (phase 0 with an even pitch is the two-per-lane body with its tail launch at odd N; everything else the one-per-lane form); wider
 ones 0, 16 and 48 bytes past a 128-byte line.  N in {1, 2, 3, 64, 257}.  Each case asserts the return code, arena.check() and the
-values (the model's, shared with tests/test_gpu_triples.py).
+values (the model's: triples_reference of tests/gpu_support.py, shared with tests/test_gpu_triples.py).
 
 TABLE has one row per entry point; test_every_device_entry_point_has_a_row reads the header and fails when a prototype that
 takes a `_dev` pointer has none."""
-import os
-import re
-
 import numpy as np
 import pytest
-import torch
 
 import oracle_lib as O
 import redzone as R
-from test_gpu_beaver import fname
-from test_gpu_triples import SEED, reference
+from abi_support import PREP, device_entry_points
+from gpu_support import TRIPLES_SEED as SEED
+from gpu_support import triples_reference as reference
+from gpu_support import el, fname, gpu_env, mat, placements, settle
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 RINGS = [O.Z2K(62), O.Z2K(128)]
 NS = [1, 2, 3, 64, 257]
-OK = 0
-
-
-def limbs(f):
-    return O.LIMBS[f]
-
-
-def esz(f):
-    return 8 * limbs(f)
-
-
-def placements(f, N, k):
-    """(align, phase in bytes, pitch in elements): one limb -- both phases, the pitch even and odd in turn; wider -- two of the
-    three phases in rotation at a pitch of N + 3"""
-    if limbs(f) == 1:
-        even = N + 2 + (N % 2)
-        return [(16, 0, even), (16, 0, even + 1), (16, 8, even), (16, 8, even + 1)]
-    return [(128, (0, 16, 48)[(k + i) % 3], N + 3) for i in (0, 1)]
-
-
-def mat(A, name, f, rows, N, pitch, align, phase):
-    return A.window(name, N * esz(f), align, phase, rows=rows, pitch_bytes=pitch * esz(f), kind="out")
-
-
-def el(w, f):
-    return w.read(np.uint64).reshape(w.rows, -1, limbs(f))
-
-
-def settle(lib, A, rc, note):
-    assert rc == OK, f"{note}: status {rc} ({lib.scl_prep_last_error().decode()})"
-    try:
-        A.check()
-    except R.RedZoneError as e:
-        raise R.RedZoneError(f"{note}\n{e}", e.strays, e.count) from None
 
 
 def run_additive(env, f):
@@ -73,7 +36,7 @@ def run_additive(env, f):
                 A = R.Arena()
                 wa, wb, wc = [mat(A, nm, f, n, N, pitch, align, phase) for nm in "abc"]
                 rc = prep.lib.scl_prep_triples_additive_prg(f, wa.ptr, wb.ptr, wc.ptr, pitch, N, n, SEED, len(SEED), 0, None)
-                settle(prep.lib, A, rc, note)
+                settle(prep.lib.scl_prep_last_error, A, rc, note)
                 for w, m, nm in zip((wa, wb, wc), want, "abc"):
                     assert np.array_equal(el(w, f), m[:, :N]), f"{note}: {nm}"
 
@@ -96,7 +59,7 @@ def run_shamir(env, f):
                 ws = A.window("scratch", need, 16, 0, kind="out") if need else None
                 rc = prep.lib.scl_prep_triples_shamir_prg(f, wa.ptr, wb.ptr, wc.ptr, pitch, N, t, n, SEED, len(SEED), 0,
                                                           ws.ptr if ws else None, flags, None)
-                settle(prep.lib, A, rc, note)
+                settle(prep.lib.scl_prep_last_error, A, rc, note)
                 for w, m, nm in zip((wa, wb, wc), want, "abc"):
                     assert np.array_equal(el(w, f), m[:, :N]), f"{note}: {nm}"
 
@@ -105,27 +68,14 @@ TABLE = {"scl_prep_triples_additive_prg": run_additive, "scl_prep_triples_shamir
 CASES = [(entry, f) for entry in TABLE for f in FIELDS + (RINGS if entry.endswith("additive_prg") else [])]
 
 
-def device_entry_points():
-    """the scl_prep_* prototypes of the header that take a `_dev` pointer"""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip_prep.h")).read(), flags=re.S)
-    return sorted(m.group(1) for m in re.finditer(r"\b(scl_prep_\w+)\s*\(([^;{]*?)\)\s*;", src) if re.search(r"\*\s*\w+_dev\b", m.group(2)))
-
-
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.prep as prep
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, prep, port
+    return gpu_env("prep")
 
 
 def test_every_device_entry_point_has_a_row():
     """(reads the header and the table: needs no GPU)"""
-    names = device_entry_points()
+    names = device_entry_points(PREP)
     assert len(names) == 2 and sorted(TABLE) == names, sorted(set(TABLE) ^ set(names))
     assert all(any(e == n for e, _ in CASES) for n in names)
 

@@ -34,7 +34,7 @@ import pytest
 
 import oracle_lib as O
 import redzone as R
-from test_merkle_host import model_levels, model_path, model_tree_bytes, sha
+from merkle_model import model_levels, model_path, model_tree_bytes, sha
 
 import torch
 

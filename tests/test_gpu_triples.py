@@ -1,5 +1,5 @@
-"""The triple dealer on the GPU (scl_amd.prep over libscl_hip_prep.so) against the Python model of tests/test_triples_host.py, which
-that file pins to what the reference dealt: device output equals the model byte for byte.
+"""The triple dealer on the GPU (scl_amd.prep over libscl_hip_prep.so) against the Python model of tests/port_models.py, which
+tests/test_triples_host.py pins to what the reference dealt: device output equals the model byte for byte.
 
 Shapes: N in {1, 2, 3, 64, 257} -- one triple, one pair (the two-per-lane form of Mersenne61), a pair and the tail launch, a
 wavefront, a block and one; additive n in {2, 3, 5}; Shamir (4,1), (10,3), (16,7) -- fused for Mersenne61, Mersenne127 and
@@ -17,9 +17,11 @@ import pytest
 import torch
 
 import oracle_lib as O
-from test_gpu_beaver import fname, host, rnd
-from test_triples_host import (additive_blocks, from_hex, golden, model_additive, model_shamir, protocol_from_model, shamir_blocks,
-                               triples_binary)
+from cxx_support import mirror_binary
+from gpu_support import TRIPLES_N, fname, gpu_env, host, rnd
+from gpu_support import TRIPLES_SEED as SEED
+from gpu_support import triples_reference as reference
+from port_models import additive_blocks, from_hex, golden, model_shamir, protocol_from_model, shamir_blocks
 
 pytestmark = pytest.mark.gpu
 
@@ -28,33 +30,14 @@ RINGS = [O.Z2K(1), O.Z2K(62), O.Z2K(64), O.Z2K(65), O.Z2K(128)]
 FUSED_FIELDS = [O.M61, O.M127, O.GF2_128]
 NS = [1, 2, 3, 64, 257]
 NMAX = max(NS)
+assert NMAX == TRIPLES_N          # the shape of the shared reference (tests/gpu_support.py)
 ADDITIVE_N = [2, 3, 5]
 SHAMIR_NT = [(4, 1), (10, 3), (16, 7), (20, 9)]
-SEED = b"gpu triples"
 
 
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.mpc as mpc
-    import scl_amd.prep as prep
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, mpc, prep, port
-
-
-_REF = {}
-
-
-def reference(port, f, n, t=None, counter0=0, N=NMAX):
-    """the model's a, b, c [n][N][L] (t None: additive), once per case"""
-    key = (f, n, t, counter0, N)
-    if key not in _REF:
-        _REF[key] = model_additive(port, f, SEED, counter0, N, n) if t is None else model_shamir(port, f, SEED, counter0, N, t, n)
-    return _REF[key]
+    return gpu_env("mpc", "prep")
 
 
 def same(got, want, N, note):
@@ -155,7 +138,7 @@ def test_the_references_protocol_test_end_to_end_on_the_device(env):
     blocks 0 and 1, the triple dealt at block 2, mask, open, finish (party 0 adds e d), recover: every value is the fixture's, the
     product is 462"""
     scl, mpc, prep, port = env
-    f, g, seed = O.M61, golden()["protocol"], b""
+    f, g, seed = O.M61, golden("triples")["protocol"], b""
     x, y = scl.to_device(port.from_int(f, 42)[None]), scl.to_device(port.from_int(f, 11)[None])
     xs = scl.additive_share_prg(f, x, 2, seed, counter0=0)
     ys = scl.additive_share_prg(f, y, 2, seed, counter0=1)
@@ -295,5 +278,5 @@ def test_wrapper_refuses_what_the_header_refuses(env):
 def test_cxx_round_trips(env):
     """tests/cxx/test_triples_api.cc --gpu: hip::dealTriplesAdditive / dealTriplesShamir equal the per-secret calls on one PRG,
     and deal, mask, open, finish, recover multiplies"""
-    r = subprocess.run([triples_binary(), "--gpu"], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([mirror_binary("triples"), "--gpu"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -1,5 +1,5 @@
-"""Batch verification on the GPU (scl_amd.vf over libscl_hip_vf.so) against the Python model of tests/test_vf_host.py, which that
-file pins to what the reference produced: device output equals the model byte for byte.  Each test's docstring names its
+"""Batch verification on the GPU (scl_amd.vf over libscl_hip_vf.so) against the Python model of tests/port_models.py, which
+tests/test_vf_host.py pins to what the reference produced: device output equals the model byte for byte.  Each test's docstring names its
 shapes.  One model run per field -- out[r][j] depends on row r and coefficient vector j alone, so every smaller row count and
 repetition count is a slice of the largest -- and one upload; every layout is a device copy of it."""
 import numpy as np
@@ -7,11 +7,10 @@ import pytest
 import torch
 
 import oracle_lib as O
-from test_gpu_beaver import fname, host
-from test_gpu_hm import pm1, pool
-from test_gpu_ip import only_the_view_was_written, placed
-from test_vf_host import (TAGS, coin_blocks, degree_entry, golden, hex_rows, model_coins, model_combine, product_entry)
-from test_triples_host import from_hex
+from cxx_support import mirror_binary
+from gpu_support import fname, gpu_env, host, only_the_view_was_written, placed, pm1, pool
+from port_models import TAGS3 as TAGS
+from port_models import coin_blocks, degree_entry, from_hex, golden, hex_rows, model_coins, model_combine, product_entry
 
 pytestmark = pytest.mark.gpu
 
@@ -24,16 +23,7 @@ SEED, C0 = b"vf gpu coin", 5                # a non-zero block counter
 
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.hm as hm
-    import scl_amd.prep as prep
-    import scl_amd.vf as vf
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, vf, hm, prep, port
+    return gpu_env("vf", "hm", "prep")
 
 
 def row_counts(vf, f, reps, prg):
@@ -232,7 +222,7 @@ def test_the_fixture_end_to_end_on_the_device(env):
     """the reference's combinations (the first N columns of rows 5 apart), its degree check -- check_degree passes on the good
     sharings, opens the reference's value and reports the altered one -- and its product check"""
     scl, vf, hm, prep, port = env
-    g = golden()
+    g = golden("vf")
     for e in g["combine"]:
         f = TAGS[e["field"]]
         x, y = scl.to_device(hex_rows(port, f, e["x"])), scl.to_device(hex_rows(port, f, e["y"]))
@@ -406,6 +396,5 @@ def test_the_cxx_round_trip(env):
     (which equals vf_combine_one), plain and product, for Mersenne61 (fused, past one trip), Mersenne127 and the secp256k1 order
     (two launches); share -> combinePrg -> shamirRecoverD opens sum rho secret and reports an altered share"""
     import subprocess
-    from test_vf_host import vf_binary
-    r = subprocess.run([vf_binary(), "--gpu"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([mirror_binary("vf"), "--gpu"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and " 0 failures" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]

@@ -7,9 +7,8 @@ import pytest
 import torch
 
 import oracle_lib as O
-from test_gpu_beaver import fname, host
-from test_gpu_hm import pool
-from test_vf_host import model_combine
+from gpu_support import fname, gpu_env, host, pool
+from port_models import model_combine
 
 pytestmark = pytest.mark.gpu
 
@@ -19,14 +18,7 @@ ERR_BAD_ARG = 3
 
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.vf as vf
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, vf, port
+    return gpu_env("vf")
 
 
 @pytest.mark.parametrize("f", FIELDS, ids=fname)

@@ -10,33 +10,18 @@ and product.  Each case asserts the return code, arena.check() and the values (t
 
 TABLE has one row per entry point; test_every_device_entry_point_has_a_row reads the header and fails when a prototype that takes
 a `_dev` pointer has none."""
-import os
-import re
-
 import numpy as np
 import pytest
-import torch
 
 import oracle_lib as O
 import redzone as R
-from test_gpu_beaver import fname
-from test_gpu_hm import pool
-from test_gpu_hm_redzones import el, esz, limbs, mat, placements
-from test_vf_host import model_coins, model_combine
+from abi_support import VF, device_entry_points
+from gpu_support import el, fname, gpu_env, limbs, mat, placements, pool, settle
+from port_models import model_coins, model_combine
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 NS = [1, 2, 3, 64, 257]
-OK = 0
 SEED, C0 = b"vf redzone coin", 3
-
-
-def settle(lib, A, rc, note):
-    assert rc == OK, f"{note}: status {rc} ({lib.scl_vf_last_error().decode()})"
-    try:
-        A.check()
-    except R.RedZoneError as e:
-        raise R.RedZoneError(f"{note}\n{e}", e.strays, e.count) from None
 
 
 def run(env, f, prg):
@@ -66,7 +51,7 @@ def run(env, f, prg):
                             wr = mat(A, "rho", f, reps, N, pitch, align, phase, "in", rho)
                             rc = vf.lib.scl_vf_combine(f, wo.ptr, reps + 3, wx.ptr, wy.ptr if prod else None, pitch, wr.ptr, pitch, rows, N, reps, ws.ptr,
                                                        need, None)
-                        settle(vf.lib, A, rc, note)
+                        settle(vf.lib.scl_vf_last_error, A, rc, note)
                         assert np.array_equal(el(wo, f), want[prod]), note
 
 
@@ -74,27 +59,14 @@ TABLE = {"scl_vf_combine_prg": lambda env, f: run(env, f, True), "scl_vf_combine
 CASES = [(entry, f) for entry in TABLE for f in FIELDS]
 
 
-def device_entry_points():
-    """the scl_vf_* prototypes of the header that take a `_dev` pointer"""
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip_vf.h")).read(), flags=re.S)
-    return sorted(m.group(1) for m in re.finditer(r"\b(scl_vf_\w+)\s*\(([^;{]*?)\)\s*;", src) if re.search(r"\*\s*\w+_dev\b", m.group(2)))
-
-
 @pytest.fixture(scope="module")
 def env():
-    if not torch.cuda.is_available():
-        pytest.fail("gpu tests need a GPU")
-    import scl_amd
-    import scl_amd.vf as vf
-    port = O.Port()
-    scl_amd.set_mont128_prime((1 << 128) - 159)
-    port.mont128_set_prime((1 << 128) - 159)
-    return scl_amd, vf, port
+    return gpu_env("vf")
 
 
 def test_every_device_entry_point_has_a_row():
     """(reads the header and the table: needs no GPU)"""
-    names = device_entry_points()
+    names = device_entry_points(VF)
     assert len(names) == 2 and sorted(TABLE) == names, sorted(set(TABLE) ^ set(names))
     assert all(any(e == n for e, _ in CASES) for n in names)
 

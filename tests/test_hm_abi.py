@@ -3,18 +3,14 @@ include/scl_hip_hm.h, the binding takes its ctypes prototypes from that header, 
 every error the header promises is decided on the host, before a launch -- so each is reachable here, without a device, with
 pointers that are never dereferenced."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from abi_support import (ERR_BAD_ARG, ERR_NO_DEVICE, ERR_SIZE_MISMATCH, OK, HM, check_engine_is_only_dependency, check_exports, check_latch_rule,
+                         declared_symbols, expect, reaches_the_device_check)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "libscl_hip_hm.so")
-OK, ERR_SIZE_MISMATCH, ERR_BAD_ARG, ERR_NO_DEVICE = 0, 1, 3, 5
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 RINGS = [O.Z2K(1), O.Z2K(64), O.Z2K(65), O.Z2K(128)]
 BASE = 1 << 24      # a 16-byte aligned address that is never read: every case below ends before a launch
@@ -28,12 +24,6 @@ SYMBOLS = ["scl_hm_abi_version", "scl_hm_apply", "scl_hm_double_blocks", "scl_hm
 def hm():
     import scl_amd.hm
     return scl_amd.hm
-
-
-def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "scl_hip_hm.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_hm_\w+)\s*\(", src)))
 
 
 def esz(f):
@@ -80,38 +70,20 @@ def entry_points(hm):
             (lib.scl_hm_mul_finish, finish_args)]
 
 
-def expect(hm, rc, want, word=None):
-    msg = hm.lib.scl_hm_last_error()
-    assert rc == want, (rc, want, msg)
-    assert msg, "scl_hm_last_error() is empty after a failure"
-    if word:
-        assert word in msg, msg
-
-
 def test_the_library_exports_the_header_and_nothing_else(hm):
-    names = declared_symbols()
-    assert names == SYMBOLS
-    out = subprocess.run(["nm", "-D", "--defined-only", SO], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert exported == set(names), sorted(exported ^ set(names))
+    check_exports(HM, SYMBOLS)
 
 
 def test_the_engine_is_its_only_project_dependency():
     """linked against libscl_hip.so, found beside it ($ORIGIN), and not against the other extension libraries; every undefined
     scl_* symbol is a prototype of scl_hip.h"""
-    dyn = subprocess.run(["readelf", "-d", SO], capture_output=True, text=True, check=True).stdout
-    assert "libscl_hip.so" in dyn and "$ORIGIN" in dyn and "libscl_hip_mpc" not in dyn and "libscl_hip_prep" not in dyn, dyn
-    und = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout
-    used = sorted({ln.split()[-1].split("@")[0] for ln in und.splitlines() if "scl_" in ln})
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(scl_hip_\w+)\s*\(", hdr))
-    assert used and set(used) <= declared, used
+    check_engine_is_only_dependency(HM)
 
 
 def test_version_and_prototypes_come_from_the_header(hm):
     assert hm.lib.scl_hm_abi_version() == 1
-    assert hm._NPROTO == len(declared_symbols()) == 8
-    for name in declared_symbols():
+    assert hm._NPROTO == len(declared_symbols(HM)) == 8
+    for name in declared_symbols(HM):
         assert getattr(hm.lib, name).argtypes is not None, name
     assert hm.lib.scl_hm_last_error.restype is C.c_char_p
     assert hm.lib.scl_hm_double_blocks.restype is C.c_size_t and hm.lib.scl_hm_double_scratch_bytes.restype is C.c_size_t
@@ -183,7 +155,7 @@ def test_nothing_to_do_is_ok_at_once(hm, f):
 def test_rings_and_unknown_tags(hm, tag):
     """Shamir needs a field: a ring is refused like an unknown tag"""
     for fn, args in entry_points(hm):
-        expect(hm, fn(*args(tag)), ERR_BAD_ARG, b"unknown field tag")
+        expect(HM, fn(*args(tag)), ERR_BAD_ARG, b"unknown field tag")
 
 
 @pytest.mark.parametrize("f", FIELDS)
@@ -193,44 +165,39 @@ def test_null_and_misaligned_pointers(hm, f):
         for i in range(k):
             p = ptrs(k)
             p[i] = None
-            expect(hm, fn(*args(f, p=p)), ERR_BAD_ARG, b"NULL")
+            expect(HM, fn(*args(f, p=p)), ERR_BAD_ARG, b"NULL")
             p = ptrs(k)
             p[i] += off
-            expect(hm, fn(*args(f, p=p)), ERR_BAD_ARG, b"aligned")
-    expect(hm, hm.lib.scl_hm_mul_finish(*finish_args(f, lam=False)), ERR_BAD_ARG, b"NULL")
+            expect(HM, fn(*args(f, p=p)), ERR_BAD_ARG, b"aligned")
+    expect(HM, hm.lib.scl_hm_mul_finish(*finish_args(f, lam=False)), ERR_BAD_ARG, b"NULL")
 
 
 @pytest.mark.parametrize("f", FIELDS)
 def test_strides_parties_thresholds_and_flags(hm, f):
     lib = hm.lib
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=8, stride=7)), ERR_SIZE_MISMATCH, b"stride < N")
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=8, stride=7)), ERR_SIZE_MISMATCH, b"stride < N")
     for n, t in ((0, 0), (2, 1), (6, 3), (1, 1)):                                  # n <= 2t: degree 2t could not be opened
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, n=n, t=t)), ERR_BAD_ARG, b"larger than 2t")
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, n=65536)), ERR_BAD_ARG, b"65535")
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, n=n, t=t)), ERR_BAD_ARG, b"larger than 2t")
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, n=65536)), ERR_BAD_ARG, b"65535")
     # a degree at which the engine's share call would synchronise the stream is refused; the last one below it is not
     tm = deg_max(f) // 2
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, t=tm + 1, n=200)), ERR_BAD_ARG, b"degree 2t must be at most %d" % deg_max(f))
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, t=65535, n=200)), ERR_BAD_ARG, b"degree")
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, t=tm, n=200, scratch=None)), ERR_BAD_ARG, b"scratch")
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, t=tm + 1, n=200)), ERR_BAD_ARG, b"degree 2t must be at most %d" % deg_max(f))
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, t=65535, n=200)), ERR_BAD_ARG, b"degree")
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, t=tm, n=200, scratch=None)), ERR_BAD_ARG, b"scratch")
     for flags in (2, 3, 0x80000000):
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, flags=flags)), ERR_BAD_ARG, b"flags")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, out_stride=7)), ERR_SIZE_MISMATCH, b"out_stride < N")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, in_stride=7)), ERR_SIZE_MISMATCH, b"in_stride < N")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, ldm=3)), ERR_SIZE_MISMATCH, b"ldm < n")
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, flags=flags)), ERR_BAD_ARG, b"flags")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, out_stride=7)), ERR_SIZE_MISMATCH, b"out_stride < N")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, in_stride=7)), ERR_SIZE_MISMATCH, b"in_stride < N")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, ldm=3)), ERR_SIZE_MISMATCH, b"ldm < n")
     for m, n in ((0, 4), (3, 0), (3, 65536)):
-        expect(hm, lib.scl_hm_apply(*apply_args(f, m=m, n=n, ldm=max(n, 1))), ERR_BAD_ARG, b"at least 1")
-    expect(hm, lib.scl_hm_mul_mask(*mask_args(f, d_stride=7)), ERR_SIZE_MISMATCH, b"d_stride < N")
-    expect(hm, lib.scl_hm_mul_mask(*mask_args(f, op_stride=7)), ERR_SIZE_MISMATCH, b"op_stride < N")
+        expect(HM, lib.scl_hm_apply(*apply_args(f, m=m, n=n, ldm=max(n, 1))), ERR_BAD_ARG, b"at least 1")
+    expect(HM, lib.scl_hm_mul_mask(*mask_args(f, d_stride=7)), ERR_SIZE_MISMATCH, b"d_stride < N")
+    expect(HM, lib.scl_hm_mul_mask(*mask_args(f, op_stride=7)), ERR_SIZE_MISMATCH, b"op_stride < N")
     for kw, word in (("z_stride", b"z_stride < N"), ("d_stride", b"d_stride < N"), ("r_stride", b"r_stride < N")):
-        expect(hm, lib.scl_hm_mul_finish(*finish_args(f, **{kw: 7})), ERR_SIZE_MISMATCH, word)
+        expect(HM, lib.scl_hm_mul_finish(*finish_args(f, **{kw: 7})), ERR_SIZE_MISMATCH, word)
     for m in (0, 65, 1000):                                                        # lambda travels with the launch: 1..64
-        expect(hm, lib.scl_hm_mul_finish(*finish_args(f, m=m)), ERR_BAD_ARG, b"1..64")
+        expect(HM, lib.scl_hm_mul_finish(*finish_args(f, m=m)), ERR_BAD_ARG, b"1..64")
         assert b"scl_hip_shamir_recover" in lib.scl_hm_last_error() and b"scl_hip_ew" in lib.scl_hm_last_error()
-
-
-def reaches_the_device_check(hm, rc):
-    """a call whose arguments are in order asks for a device next; with a GPU present these addresses must not get that far"""
-    assert rc == ERR_NO_DEVICE, (rc, hm.lib.scl_hm_last_error())
 
 
 @pytest.mark.parametrize("f", [O.M61, O.SECP256K1_SCALAR])
@@ -245,24 +212,24 @@ def test_overlaps_and_the_allowed_aliases(hm, f):
     for i, j in ((0, 1), (1, 0)):
         p = ptrs(2)
         p[j] = p[i] + ((n - 1) * N + N - 1) * e          # starts at the last element of the other matrix
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=n, p=p)), ERR_BAD_ARG, b"overlap")
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=n, p=p)), ERR_BAD_ARG, b"overlap")
         p[j] = p[i] + n * N * e                           # back to back is in order: the check AFTER the overlap check is met
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=n, p=p, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=n, p=p, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
     need = lib.scl_hm_double_scratch_bytes(f, N, 12, 4, 0)
     assert need == 13 * N * e
     for k in range(2):
         p = ptrs(2)
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=12, t=4, p=p, scratch=p[k] + ((12 * N - 1) * e & ~15))), ERR_BAD_ARG,
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=12, t=4, p=p, scratch=p[k] + ((12 * N - 1) * e & ~15))), ERR_BAD_ARG,
                b"scratch overlaps")
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=12, t=4, p=p, scratch=p[k] - need + 16)), ERR_BAD_ARG, b"scratch overlaps")
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=N, n=12, t=4, p=p, scratch=p[k] - need + 16)), ERR_BAD_ARG, b"scratch overlaps")
     # apply: out against in and against M, with and without batches
     m, n = 3, 4
     out, inp, M = ptrs(3)
-    expect(hm, lib.scl_hm_apply(*apply_args(f, N=N, p=[inp + (n * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, N=N, p=[inp - (m * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, N=N, p=[M + (m * n - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps M")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, N=N, batch=5, p=[inp + (5 * n * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
-    expect(hm, lib.scl_hm_apply(*apply_args(f, N=N, batch=5, p=[inp - (5 * m * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, N=N, p=[inp + (n * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, N=N, p=[inp - (m * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, N=N, p=[M + (m * n - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps M")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, N=N, batch=5, p=[inp + (5 * n * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
+    expect(HM, lib.scl_hm_apply(*apply_args(f, N=N, batch=5, p=[inp - (5 * m * N - 1) * e, inp, M])), ERR_BAD_ARG, b"out overlaps in")
     # mask: d against x and y; d == r2 only exactly
     d, x, y, r2 = ptrs(4)
     rows = 3
@@ -270,21 +237,21 @@ def test_overlaps_and_the_allowed_aliases(hm, f):
         for delta in ((rows * N - 1) * e, -(rows * N - 1) * e, 32 if k == 3 else 0):     # (d == r2 exactly is the allowed alias)
             p = [d, x, y, r2]
             p[k] = d + (delta & ~15 if delta > 0 else -((-delta) & ~15))
-            expect(hm, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG, word)
-    expect(hm, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, x, y, d], d_stride=N + 2, op_stride=N)), ERR_BAD_ARG, b"d overlaps r2")
+            expect(HM, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG, word)
+    expect(HM, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, x, y, d], d_stride=N + 2, op_stride=N)), ERR_BAD_ARG, b"d overlaps r2")
     # finish: z against dsh; z == r only exactly
     z, dsh, r = ptrs(3)
-    expect(hm, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[dsh + ((4 * N - 1) * e & ~15), dsh, r])), ERR_BAD_ARG, b"z overlaps dsh")
-    expect(hm, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, z, r])), ERR_BAD_ARG, b"z overlaps dsh")
-    expect(hm, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z + 16 * 2])), ERR_BAD_ARG, b"z overlaps r")
-    expect(hm, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z], z_stride=N + 2, r_stride=N)), ERR_BAD_ARG, b"z overlaps r")
+    expect(HM, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[dsh + ((4 * N - 1) * e & ~15), dsh, r])), ERR_BAD_ARG, b"z overlaps dsh")
+    expect(HM, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, z, r])), ERR_BAD_ARG, b"z overlaps dsh")
+    expect(HM, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z + 16 * 2])), ERR_BAD_ARG, b"z overlaps r")
+    expect(HM, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z], z_stride=N + 2, r_stride=N)), ERR_BAD_ARG, b"z overlaps r")
     if no_gpu:
-        reaches_the_device_check(hm, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, x, y, d])))                      # d == r2
-        reaches_the_device_check(hm, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, x, y, d], d_stride=N + 2, op_stride=N + 2)))
-        reaches_the_device_check(hm, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z])))                              # z == r
-        reaches_the_device_check(hm, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z], z_stride=N + 2, r_stride=N + 2)))
-        reaches_the_device_check(hm, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, d + rows * N * e, y, r2])))      # back to back
-        reaches_the_device_check(hm, lib.scl_hm_apply(*apply_args(f, N=N, p=[inp + n * N * e, inp, M])))
+        reaches_the_device_check(HM, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, x, y, d])))                      # d == r2
+        reaches_the_device_check(HM, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, x, y, d], d_stride=N + 2, op_stride=N + 2)))
+        reaches_the_device_check(HM, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z])))                              # z == r
+        reaches_the_device_check(HM, lib.scl_hm_mul_finish(*finish_args(f, N=N, p=[z, dsh, z], z_stride=N + 2, r_stride=N + 2)))
+        reaches_the_device_check(HM, lib.scl_hm_mul_mask(*mask_args(f, N=N, rows=rows, p=[d, d + rows * N * e, y, r2])))      # back to back
+        reaches_the_device_check(HM, lib.scl_hm_apply(*apply_args(f, N=N, p=[inp + n * N * e, inp, M])))
 
 
 def test_a_two_pass_case_without_scratch_names_the_size_it_needs(hm):
@@ -293,15 +260,15 @@ def test_a_two_pass_case_without_scratch_names_the_size_it_needs(hm):
     for f, t, flags in cases:
         need = lib.scl_hm_double_scratch_bytes(f, 257, 20, t, flags)
         assert need == (1 + 3 * t) * 257 * esz(f)
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=257, t=t, n=20, scratch=None, flags=flags)), ERR_BAD_ARG, str(need).encode())
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=257, t=t, n=20, scratch=None, flags=flags)), ERR_BAD_ARG, str(need).encode())
         assert b"scratch" in lib.scl_hm_last_error()
-        expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=257, t=t, n=20, scratch=BASE + (8 << 20) + 8, flags=flags)), ERR_BAD_ARG,
+        expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=257, t=t, n=20, scratch=BASE + (8 << 20) + 8, flags=flags)), ERR_BAD_ARG,
                b"aligned")
 
 
 def test_a_block_range_that_wraps_the_counter_is_refused(hm):
-    expect(hm, hm.lib.scl_hm_double_share_prg(*double_args(O.M61, N=8, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
-    expect(hm, hm.lib.scl_hm_double_share_prg(*double_args(O.SECP256K1_FIELD, N=2 ** 60, stride=2 ** 60, n=4, counter0=0)), ERR_BAD_ARG)
+    expect(HM, hm.lib.scl_hm_double_share_prg(*double_args(O.M61, N=8, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
+    expect(HM, hm.lib.scl_hm_double_share_prg(*double_args(O.SECP256K1_FIELD, N=2 ** 60, stride=2 ** 60, n=4, counter0=0)), ERR_BAD_ARG)
 
 
 @pytest.mark.parametrize("f", FIELDS)
@@ -313,42 +280,20 @@ def test_a_well_formed_call_needs_a_device(hm, f):
     if torch.cuda.is_available():
         pytest.skip("GPU present: these addresses must not reach a kernel")
     lib = hm.lib
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=8, t=3, n=10, stride=11, counter0=2 ** 32 - 5)), ERR_NO_DEVICE)
-    expect(hm, lib.scl_hm_double_share_prg(*double_args(f, N=8, t=4, n=9, stride=8, flags=TWO_PASS)), ERR_NO_DEVICE)
-    expect(hm, lib.scl_hm_apply(*apply_args(f, N=8, m=7, n=10, batch=10, ldm=12, out_stride=9, in_stride=90)), ERR_NO_DEVICE)
-    expect(hm, lib.scl_hm_mul_mask(*mask_args(f, d_stride=9, op_stride=11)), ERR_NO_DEVICE)
-    expect(hm, lib.scl_hm_mul_finish(*finish_args(f, m=64, z_stride=9, d_stride=10, r_stride=11)), ERR_NO_DEVICE)
-    expect(hm, lib.scl_hm_mul_finish(*finish_args(f, m=1)), ERR_NO_DEVICE)
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=8, t=3, n=10, stride=11, counter0=2 ** 32 - 5)), ERR_NO_DEVICE)
+    expect(HM, lib.scl_hm_double_share_prg(*double_args(f, N=8, t=4, n=9, stride=8, flags=TWO_PASS)), ERR_NO_DEVICE)
+    expect(HM, lib.scl_hm_apply(*apply_args(f, N=8, m=7, n=10, batch=10, ldm=12, out_stride=9, in_stride=90)), ERR_NO_DEVICE)
+    expect(HM, lib.scl_hm_mul_mask(*mask_args(f, d_stride=9, op_stride=11)), ERR_NO_DEVICE)
+    expect(HM, lib.scl_hm_mul_finish(*finish_args(f, m=64, z_stride=9, d_stride=10, r_stride=11)), ERR_NO_DEVICE)
+    expect(HM, lib.scl_hm_mul_finish(*finish_args(f, m=1)), ERR_NO_DEVICE)
 
 
 def test_mont128_honours_the_latch_rule(hm):
     """scl_hip_mont128_set_prime's rule reaches the extension: a worker whose latched default went stale is refused (the engine's
     own check and message) until it re-latches; the main thread, which set its own modulus, is not disturbed"""
-    from concurrent.futures import ThreadPoolExecutor
-    import scl_amd as scl
-    p0, p1 = 2 ** 128 - 159, 2 ** 127 - 1
     lib = hm.lib
-    bad = [(lib.scl_hm_double_share_prg, double_args(O.MONT128, flags=2), b"flags"),            # calls that end at a later check
-           (lib.scl_hm_apply, apply_args(O.MONT128, m=0), b"at least 1"),                        # when the modulus is in order
-           (lib.scl_hm_mul_mask, mask_args(O.MONT128, d_stride=7), b"d_stride"),
-           (lib.scl_hm_mul_finish, finish_args(O.MONT128, m=65), b"1..64")]
-
-    def call(fn, args):
-        rc = fn(*args)
-        return rc, lib.scl_hm_last_error()
-    try:
-        for fn, args, word in bad:
-            scl.set_mont128_prime(p0)
-            with ThreadPoolExecutor(max_workers=1) as worker:
-                assert worker.submit(scl.mont128_prime).result() == p0     # the worker latches the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc != OK and word in msg
-                scl.set_mont128_prime(p1)                                  # the main thread moves the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc == ERR_BAD_ARG and b"latched" in msg
-                assert word in call(fn, args)[1]                           # the main thread goes on
-                worker.submit(scl.mont128_relatch).result()
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc != OK and word in msg
-    finally:
-        scl.set_mont128_prime(p0)
+    # calls that end at a later check when the modulus is in order
+    check_latch_rule(HM, [(lib.scl_hm_double_share_prg, double_args(O.MONT128, flags=2), b"flags", ERR_BAD_ARG),
+                          (lib.scl_hm_apply, apply_args(O.MONT128, m=0), b"at least 1", ERR_BAD_ARG),
+                          (lib.scl_hm_mul_mask, mask_args(O.MONT128, d_stride=7), b"d_stride", ERR_SIZE_MISMATCH),
+                          (lib.scl_hm_mul_finish, finish_args(O.MONT128, m=65), b"1..64", ERR_BAD_ARG)])

@@ -3,17 +3,14 @@ include/scl_hip_ip.h, the binding takes its ctypes prototypes from that header, 
 every error the header promises is decided on the host, before a launch -- so each is reachable here, without a device, with
 pointers that are never dereferenced."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import pytest
 
 import oracle_lib as O
+from abi_support import (ERR_BAD_ARG, ERR_NO_DEVICE, ERR_SIZE_MISMATCH, OK, IP, check_engine_is_only_dependency, check_exports,
+                         check_last_error_per_thread, check_latch_rule, declared_symbols, expect, header, reaches_the_device_check)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "libscl_hip_ip.so")
-OK, ERR_SIZE_MISMATCH, ERR_BAD_ARG, ERR_NO_DEVICE = 0, 1, 3, 5
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 RINGS = [O.Z2K(1), O.Z2K(64), O.Z2K(65), O.Z2K(128)]
 BASE = 1 << 24      # a 16-byte aligned address that is never read: every case below ends before a launch
@@ -25,15 +22,6 @@ TILES = {1: (4, 4), 2: (2, 4), 4: (2, 2)}      # by limbs, as the header states 
 def ip():
     import scl_amd.ip
     return scl_amd.ip
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "scl_hip_ip.h")).read()
-
-
-def declared_symbols():
-    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_ip_\w+)\s*\(", src)))
 
 
 def esz(f):
@@ -62,40 +50,20 @@ def entry_points(ip):
     return [(ip.lib.scl_ip_dot_mask, dot_args), (ip.lib.scl_ip_matmul_mask, mat_args)]
 
 
-def expect(ip, rc, want, *words):
-    msg = ip.lib.scl_ip_last_error()
-    assert rc == want, (rc, want, msg)
-    assert msg, "scl_ip_last_error() is empty after a failure"
-    for w in words:
-        assert w in msg, msg
-
-
 def test_the_library_exports_the_header_and_nothing_else(ip):
-    names = declared_symbols()
-    assert names == SYMBOLS
-    out = subprocess.run(["nm", "-D", "--defined-only", SO], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert exported == set(names), sorted(exported ^ set(names))
-    listed = re.findall(r"^\s+(scl_ip_\w+);", open(os.path.join(ROOT, "secure-computation-library_amd", "csrc", "exports_ip.map")).read(), flags=re.M)
-    assert sorted(listed) == names
+    check_exports(IP, SYMBOLS)
 
 
 def test_the_engine_is_its_only_project_dependency():
     """linked against libscl_hip.so, found beside it ($ORIGIN), and not against the other extension libraries; every undefined
     scl_* symbol is a prototype of scl_hip.h"""
-    dyn = subprocess.run(["readelf", "-d", SO], capture_output=True, text=True, check=True).stdout
-    assert "libscl_hip.so" in dyn and "$ORIGIN" in dyn and not any(x in dyn for x in ("libscl_hip_mpc", "libscl_hip_prep", "libscl_hip_hm")), dyn
-    und = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout
-    used = sorted({ln.split()[-1].split("@")[0] for ln in und.splitlines() if "scl_" in ln})
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(scl_hip_\w+)\s*\(", hdr))
-    assert used and set(used) <= declared, used
+    check_engine_is_only_dependency(IP)
 
 
 def test_version_and_prototypes_come_from_the_header(ip):
-    assert ip.lib.scl_ip_abi_version() == 1 and re.search(r"#define\s+SCL_IP_ABI_VERSION\s+1\b", header())
-    assert ip._NPROTO == len(declared_symbols()) == 5
-    for name in declared_symbols():
+    assert ip.lib.scl_ip_abi_version() == 1 and re.search(r"#define\s+SCL_IP_ABI_VERSION\s+1\b", header(IP))
+    assert ip._NPROTO == len(declared_symbols(IP)) == 5
+    for name in declared_symbols(IP):
         assert getattr(ip.lib, name).argtypes is not None, name
     assert ip.lib.scl_ip_last_error.restype is C.c_char_p and ip.lib.scl_ip_matmul_tile.restype is None
     d, m, t = ip.lib.scl_ip_dot_mask.argtypes, ip.lib.scl_ip_matmul_mask.argtypes, ip.lib.scl_ip_matmul_tile.argtypes
@@ -113,7 +81,7 @@ def test_version_and_prototypes_come_from_the_header(ip):
 def test_the_tile_query_agrees_with_the_header(ip):
     """4 x 4 for Mersenne61, 2 x 4 for the 16-byte fields, 2 x 2 for the 32-byte fields -- the header's sentence --; 0 x 0 for
     what the call refuses; a NULL out-pointer is skipped"""
-    text = " ".join(header().split())
+    text = " ".join(header(IP).split())
     assert "4 x 4 for Mersenne61, 2 x 4 for the 16-byte fields, 2 x 2 for the 32-byte fields" in text
     assert "ceil(b/TL) a K + ceil(a/TI) K b + 2 a b" in text
     for f in FIELDS:
@@ -144,7 +112,7 @@ def test_nothing_to_do_is_ok_at_once(ip, f):
 def test_rings_and_unknown_tags(ip, tag):
     """Shamir needs a field: a ring is refused like an unknown tag"""
     for fn, args in entry_points(ip):
-        expect(ip, fn(*args(tag)), ERR_BAD_ARG, b"unknown field tag")
+        expect(IP, fn(*args(tag)), ERR_BAD_ARG, b"unknown field tag")
 
 
 @pytest.mark.parametrize("f", FIELDS)
@@ -156,33 +124,28 @@ def test_null_and_misaligned_pointers(ip, f):
             p = ptrs(4)
             p[i] = None
             if i < 3:
-                expect(ip, fn(*args(f, p=p)), ERR_BAD_ARG, b"NULL")
+                expect(IP, fn(*args(f, p=p)), ERR_BAD_ARG, b"NULL")
             p = ptrs(4)
             p[i] += off
-            expect(ip, fn(*args(f, p=p)), ERR_BAD_ARG, b"aligned")
+            expect(IP, fn(*args(f, p=p)), ERR_BAD_ARG, b"aligned")
 
 
 @pytest.mark.parametrize("f", FIELDS)
 def test_strides_terms_and_dimensions(ip, f):
     lib = ip.lib
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, terms=0)), ERR_BAD_ARG, b"terms")
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, d_stride=7)), ERR_SIZE_MISMATCH, b"d_stride < N")
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, op_stride=7)), ERR_SIZE_MISMATCH, b"op_stride < N")
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, terms=2 ** 40, xts=2 ** 40)), ERR_BAD_ARG, b"extent of x_dev overflows")
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, rows=2 ** 40, d_stride=2 ** 40)), ERR_BAD_ARG, b"extent of d_dev overflows")
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, terms=0)), ERR_BAD_ARG, b"terms")
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, d_stride=7)), ERR_SIZE_MISMATCH, b"d_stride < N")
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, op_stride=7)), ERR_SIZE_MISMATCH, b"op_stride < N")
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, terms=2 ** 40, xts=2 ** 40)), ERR_BAD_ARG, b"extent of x_dev overflows")
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, rows=2 ** 40, d_stride=2 ** 40)), ERR_BAD_ARG, b"extent of d_dev overflows")
     for kw, word in (("ds", b"d_stride < N"), ("xs", b"x_stride < N"), ("ys", b"y_stride < N"), ("rs", b"r2_stride < N")):
-        expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, **{kw: 7})), ERR_SIZE_MISMATCH, word)
+        expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, **{kw: 7})), ERR_SIZE_MISMATCH, word)
     for a, K, b in ((0, 3, 2), (2, 0, 2), (2, 3, 0), (65536, 3, 2), (2, 65536, 2), (2, 3, 65536)):
-        expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, a=a, K=K, b=b)), ERR_BAD_ARG, b"at least 1 and at most 65535")
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, batch=3, dbs=2 * 2 * 8 - 1)), ERR_BAD_ARG, b"d_batch_stride", b"32 elements")
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, batch=2 ** 50, dbs=2 ** 20)), ERR_BAD_ARG, b"extent of d_dev overflows")
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, batch=2 ** 50, xbs=2 ** 20, dbs=32, p=[BASE, BASE + (1 << 62), BASE + (1 << 61), None])), ERR_BAD_ARG,
+        expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, a=a, K=K, b=b)), ERR_BAD_ARG, b"at least 1 and at most 65535")
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, batch=3, dbs=2 * 2 * 8 - 1)), ERR_BAD_ARG, b"d_batch_stride", b"32 elements")
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, batch=2 ** 50, dbs=2 ** 20)), ERR_BAD_ARG, b"extent of d_dev overflows")
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, batch=2 ** 50, xbs=2 ** 20, dbs=32, p=[BASE, BASE + (1 << 62), BASE + (1 << 61), None])), ERR_BAD_ARG,
            b"overflows")
-
-
-def reaches_the_device_check(ip, rc):
-    """a call whose arguments are in order asks for a device next; with a GPU present these addresses must not get that far"""
-    assert rc == ERR_NO_DEVICE, (rc, ip.lib.scl_ip_last_error())
 
 
 @pytest.mark.parametrize("f", [O.M61, O.SECP256K1_SCALAR])
@@ -200,25 +163,25 @@ def test_overlaps_and_the_allowed_aliases(ip, f):
         for off in (-span(terms * rows), span(rows), 0):      # the input's last term runs into d; the input starts in d's last row; exactly d
             p = [d, x, y, r2]
             p[k] = d + off
-            expect(ip, lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=p)), ERR_BAD_ARG, b"d_dev overlaps", name)
+            expect(IP, lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=p)), ERR_BAD_ARG, b"d_dev overlaps", name)
     for delta in (span(rows), -span(rows), 32):
-        expect(ip, lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, y, d + delta])), ERR_BAD_ARG, b"d_dev overlaps r2_dev",
+        expect(IP, lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, y, d + delta])), ERR_BAD_ARG, b"d_dev overlaps r2_dev",
                b"may coincide")
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, y, d], d_stride=N + 2)), ERR_BAD_ARG, b"d_dev overlaps r2_dev")
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, y, d], d_stride=N + 2)), ERR_BAD_ARG, b"d_dev overlaps r2_dev")
     # matmul: the same, over all batches
     a, K, b, batch = 2, 3, 2, 3
     for k, name, count in ((1, b"x_dev", batch * a * K), (2, b"y_dev", batch * K * b)):
         for off in (-span(count), span(batch * a * b), 0):
             p = [d, x, y, r2]
             p[k] = d + off
-            expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=p)), ERR_BAD_ARG, b"d_dev overlaps", name)
+            expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=p)), ERR_BAD_ARG, b"d_dev overlaps", name)
     for delta in (span(batch * a * b), -span(batch * a * b), 32):
-        expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=[d, x, y, d + delta])), ERR_BAD_ARG, b"d_dev overlaps r2_dev", b"may coincide")
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=[d, x, y, d], ds=N + 2, dbs=4 * (N + 2), rs=N, rbs=4 * (N + 2))), ERR_BAD_ARG,
+        expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=[d, x, y, d + delta])), ERR_BAD_ARG, b"d_dev overlaps r2_dev", b"may coincide")
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=[d, x, y, d], ds=N + 2, dbs=4 * (N + 2), rs=N, rbs=4 * (N + 2))), ERR_BAD_ARG,
            b"d_dev overlaps r2_dev")
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=[d, x, y, d], dbs=4 * N + 2, rbs=4 * N + 4)), ERR_BAD_ARG, b"d_dev overlaps r2_dev")
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, N=N, batch=batch, p=[d, x, y, d], dbs=4 * N + 2, rbs=4 * N + 4)), ERR_BAD_ARG, b"d_dev overlaps r2_dev")
     if no_gpu:
-        ok = lambda rc: reaches_the_device_check(ip, rc)
+        ok = lambda rc: reaches_the_device_check(IP, rc)
         ok(lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, y, d])))                                      # d == r2
         ok(lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, y, d], d_stride=N + 2, op_stride=N + 2)))
         ok(lib.scl_ip_dot_mask(*dot_args(f, N=N, rows=rows, terms=terms, p=[d, x, x, x])))                                      # inputs on one another
@@ -241,49 +204,23 @@ def test_a_well_formed_call_needs_a_device(ip, f):
     if torch.cuda.is_available():
         pytest.skip("GPU present: these addresses must not reach a kernel")
     lib = ip.lib
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, d_stride=9, op_stride=11)), ERR_NO_DEVICE)
-    expect(ip, lib.scl_ip_dot_mask(*dot_args(f, terms=1, rows=1)), ERR_NO_DEVICE)
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, a=5, K=7, b=3, batch=10, ds=9, xs=10, ys=11, rs=12)), ERR_NO_DEVICE)
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, a=1, K=7, b=1, batch=2)), ERR_NO_DEVICE)        # the inner-product route
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, d_stride=9, op_stride=11)), ERR_NO_DEVICE)
+    expect(IP, lib.scl_ip_dot_mask(*dot_args(f, terms=1, rows=1)), ERR_NO_DEVICE)
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, a=5, K=7, b=3, batch=10, ds=9, xs=10, ys=11, rs=12)), ERR_NO_DEVICE)
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, a=1, K=7, b=1, batch=2)), ERR_NO_DEVICE)        # the inner-product route
     d, x, y, _ = ptrs(4)
-    expect(ip, lib.scl_ip_matmul_mask(*mat_args(f, p=[d, x, y, None], rs=0)), ERR_NO_DEVICE)       # without r2 its stride means nothing
+    expect(IP, lib.scl_ip_matmul_mask(*mat_args(f, p=[d, x, y, None], rs=0)), ERR_NO_DEVICE)       # without r2 its stride means nothing
 
 
 def test_mont128_honours_the_latch_rule(ip):
     """scl_hip_mont128_set_prime's rule reaches the extension: a worker whose latched default went stale is refused (the engine's
     own check and message) until it re-latches; the main thread, which set its own modulus, is not disturbed"""
-    from concurrent.futures import ThreadPoolExecutor
-    import scl_amd as scl
-    p0, p1 = 2 ** 128 - 159, 2 ** 127 - 1
-    lib = ip.lib
-    bad = [(lib.scl_ip_dot_mask, dot_args(O.MONT128, terms=0), b"terms"),                  # calls that end at a later check
-           (lib.scl_ip_matmul_mask, mat_args(O.MONT128, K=0), b"at least 1")]              # when the modulus is in order
-
-    def call(fn, args):
-        rc = fn(*args)
-        return rc, lib.scl_ip_last_error()
-    try:
-        for fn, args, word in bad:
-            scl.set_mont128_prime(p0)
-            with ThreadPoolExecutor(max_workers=1) as worker:
-                assert worker.submit(scl.mont128_prime).result() == p0     # the worker latches the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc != OK and word in msg
-                scl.set_mont128_prime(p1)                                  # the main thread moves the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc == ERR_BAD_ARG and b"latched" in msg
-                assert word in call(fn, args)[1]                           # the main thread goes on
-                worker.submit(scl.mont128_relatch).result()
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc != OK and word in msg
-    finally:
-        scl.set_mont128_prime(p0)
+    # calls that end at a later check when the modulus is in order
+    check_latch_rule(IP, [(ip.lib.scl_ip_dot_mask, dot_args(O.MONT128, terms=0), b"terms", ERR_BAD_ARG),
+                          (ip.lib.scl_ip_matmul_mask, mat_args(O.MONT128, K=0), b"at least 1", ERR_BAD_ARG)])
 
 
 def test_the_last_error_is_per_thread(ip):
-    from concurrent.futures import ThreadPoolExecutor
     lib = ip.lib
-    lib.scl_ip_dot_mask(*dot_args(O.M61, terms=0))
-    with ThreadPoolExecutor(max_workers=1) as worker:
-        assert worker.submit(lambda: (lib.scl_ip_matmul_mask(*mat_args(O.M61, K=0)), lib.scl_ip_last_error())).result()[1].startswith(b"matmul_mask")
-    assert lib.scl_ip_last_error().startswith(b"dot_mask: terms")
+    check_last_error_per_thread(IP, (lib.scl_ip_dot_mask, dot_args(O.M61, terms=0)), b"dot_mask: terms",
+                                (lib.scl_ip_matmul_mask, mat_args(O.M61, K=0)), b"matmul_mask")

@@ -1,4 +1,4 @@
-"""Inner and matrix products of Shamir sharings at one opening, the host half: a Python model of the local step
+"""Inner and matrix products of Shamir sharings at one opening, the host half: the Python model (tests/port_models.py) of the local step
 [d]_2t = sum_k [x_k]_t [y_k]_t + [R]_2t built from pieces of the CPU oracle only (Port.ew; Port.dot and Port.matmul check it column
 by column), pinned entry by entry to what the REFERENCE produced (tests/golden/golden_ip.json); the same model over the fields the
 reference lacks against plain Python integers (GF(2^128): the shift-xor multiplier of the GMAC tests); the stand-alone check of the
@@ -7,83 +7,23 @@ address and undefined-behaviour sanitizers; and the C++ mirror's host mode (test
 also checks the kernels in tests/test_gpu_ip.py.  Everything is exact.
 
 The fixture's order (tests/golden/make_golden_ip.py): the inputs come off ONE util::PRG term after term -- x_k, y_k, the sharing of
-x_k, the sharing of y_k -- which is model_inputs of tests/test_hm_host.py; [R] is model_double on the seed "ip dealer"."""
+x_k, the sharing of y_k -- which is model_inputs of tests/port_models.py; [R] is model_double on the seed "ip dealer"."""
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle_lib as O
+from cxx_support import SANITIZE, host_check, mirror_binary, mirror_host_output, needed
 from extremes import gf_mul
-from test_hm_host import _newest_header, model_double, model_finish, model_inputs, model_open
-from test_triples_host import from_hex
+from port_models import TAGS3 as TAGS
+from port_models import (ew as _ew, golden, golden_path, inner_entry, matrix_entry, model_dot_mask, model_finish, model_matmul_mask,
+                         model_open)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.path.join(ROOT, "tests", "cxx")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_ip.json")
-TAGS = {"m61": O.M61, "m127": O.M127, "secp256k1_scalar": O.SECP256K1_SCALAR}
+GOLDEN = golden_path("ip")
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 MONT_P = (1 << 128) - 159
-
-
-# ---- the model ---------------------------------------------------------------------------------------------------------------
-def _ew(port, f, op, a, b):
-    L = O.LIMBS[f]
-    return port.ew(f, op, np.ascontiguousarray(a).reshape(-1, L), np.ascontiguousarray(b).reshape(-1, L)).reshape(a.shape)
-
-
-def model_dot_mask(port, f, x, y, r2=None):
-    """x, y [terms][...][L], r2 [...][L] or None -> sum_k x[k] y[k] (+ r2), one reduced operation at a time"""
-    acc = _ew(port, f, O.MUL, x[0], y[0])
-    for k in range(1, x.shape[0]):
-        acc = _ew(port, f, O.ADD, acc, _ew(port, f, O.MUL, x[k], y[k]))
-    return acc if r2 is None else _ew(port, f, O.ADD, acc, r2)
-
-
-def model_matmul_mask(port, f, X, Y, r2=None):
-    """X [batch][a][K][N][L], Y [batch][K][b][N][L], r2 [batch][a][b][N][L] or None -> [batch][a][b][N][L]"""
-    batch, a, K, N, L = X.shape
-    b = Y.shape[2]
-    out = np.zeros((batch, a, b, N, L), dtype=np.uint64)
-    for i in range(a):
-        for l in range(b):
-            out[:, i, l] = model_dot_mask(port, f, np.moveaxis(X[:, i], 1, 0), np.moveaxis(Y[:, :, l], 1, 0), None if r2 is None else r2[:, i, l])
-    return out
-
-
-# ---- the fixture ---------------------------------------------------------------------------------------------------------------
-def golden():
-    with open(GOLDEN) as fh:
-        return json.load(fh)["data"]
-
-
-def inner_entry(port, f, e):
-    """one `inner` entry: the model's operands in the device layout and what the reference recorded
-    -> xs, ys [K][n][1][L], lo, hi [n][1][L], want (dict)"""
-    n, t, K = e["n"], e["t"], e["K"]
-    x, y, xs, ys = model_inputs(port, f, b"ip inputs", K, t, n)              # xs [n][K][L]
-    assert np.array_equal(x, from_hex(port, f, e["x"])) and np.array_equal(y, from_hex(port, f, e["y"]))
-    lo, hi, _ = model_double(port, f, b"ip dealer", 0, 1, t, n)             # [n][1][L]
-    want = {k: from_hex(port, f, e["out"][k])[:, None] for k in ("d_shares", "z_shares")}
-    want.update({k: from_hex(port, f, [e["out"][k]]) for k in ("d", "z")})
-    want["x"], want["y"] = x, y
-    term_major = lambda s: np.ascontiguousarray(np.transpose(s, (1, 0, 2))[:, :, None])
-    return term_major(xs), term_major(ys), lo, hi, want
-
-
-def matrix_entry(port, f, e):
-    """one `matrix` entry -> X [n][a][K][1][L], Y [n][K][b][1][L], lo, hi [n][a][b][1][L], want"""
-    n, t, a, K, b = e["n"], e["t"], e["a"], e["K"], e["b"]
-    x, y, xs, ys = model_inputs(port, f, b"ip matrix", a * K, t, n)          # pair p: X's entry p, Y's entry p, row-major
-    assert np.array_equal(x, from_hex(port, f, e["x"])) and np.array_equal(y, from_hex(port, f, e["y"]))
-    lo, hi, _ = model_double(port, f, b"ip dealer", 0, a * b, t, n)         # [n][a b][L]
-    L = O.LIMBS[f]
-    want = {k: np.stack([from_hex(port, f, o[k]) for o in e["out"]], axis=1).reshape(n, a, b, 1, L) for k in ("d_shares", "z_shares")}
-    want.update({k: from_hex(port, f, [o[k] for o in e["out"]]) for k in ("d", "z")})
-    want["x"], want["y"] = x, y
-    return xs.reshape(n, a, K, 1, L), ys.reshape(n, K, b, 1, L), lo.reshape(n, a, b, 1, L), hi.reshape(n, a, b, 1, L), want
 
 
 @pytest.fixture(scope="module")
@@ -94,7 +34,7 @@ def port():
 
 
 def test_the_fixture_has_the_documented_shape():
-    g = golden()
+    g = golden("ip")
     assert [(e["field"], e["n"], e["t"], e["K"]) for e in g["inner"]] == [(f, n, t, K) for f in TAGS for n, t in ((4, 1), (10, 3)) for K in (1, 3, 5)]
     assert [(e["field"], e["n"], e["t"], e["a"], e["K"], e["b"]) for e in g["matrix"]] == [(f, 4, 1, 2, 3, 2) for f in TAGS]
     assert os.path.getsize(GOLDEN) < 64 * 1024
@@ -103,7 +43,7 @@ def test_the_fixture_has_the_documented_shape():
 def test_the_model_computes_the_fixtures_inner_products(port):
     """every entry: every party's d, the opened d, every party's z and the recovered z are the reference's; z is Port.dot of the
     secrets"""
-    for e in golden()["inner"]:
+    for e in golden("ip")["inner"]:
         f = TAGS[e["field"]]
         xs, ys, lo, hi, want = inner_entry(port, f, e)
         note = (e["field"], e["n"], e["K"])
@@ -120,7 +60,7 @@ def test_the_model_computes_the_fixtures_inner_products(port):
 
 def test_the_model_computes_the_fixtures_matrix_products(port):
     """2 x 3 times 3 x 2 at (4,1): every intermediate is the reference's; Z is Port.matmul of the secrets"""
-    for e in golden()["matrix"]:
+    for e in golden("ip")["matrix"]:
         f = TAGS[e["field"]]
         X, Y, lo, hi, want = matrix_entry(port, f, e)
         n, a, K, b, L = e["n"], e["a"], e["K"], e["b"], O.LIMBS[f]
@@ -180,48 +120,23 @@ def test_the_model_over_the_fields_without_a_fixture(port, f):
 
 
 # ---- the per-element forms -------------------------------------------------------------------------------------------------------
-def host_check(tmp_path, name, flags):
-    exe = str(tmp_path / name)
-    b = subprocess.run(["g++", "-std=c++20", "-w", f"-I{ROOT}/include", *flags, "-o", exe, os.path.join(CXX, "ip_host_check.cc")],
-                       capture_output=True, text=True)
-    assert b.returncode == 0, b.stderr[-3000:]
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and " 0 mismatches" in r.stdout, r.stdout + r.stderr
-    return r.stdout + r.stderr
-
-
 def test_the_per_element_forms_equal_the_reduced_operations(tmp_path):
     """every field struct: ip_mac_step / ip_finish / ip_dot_one and a tile under one count == mul and add one at a time, over 1,
     2, 3, 4, 7, 63, 64, 65, 127, 128, 129 and 300 terms, uniform and all at p - 1, with and without the addend; the term count
     never passes the field's bound and the addend folds first exactly when the bound is met"""
-    host_check(tmp_path, "ip_host_check", ["-O2"])
+    host_check(tmp_path, "ip_host_check.cc", "ip_host_check", ("-w", "-O2"))
 
 
 def test_the_per_element_forms_under_the_sanitizers(tmp_path):
     """the same stand-alone program under -fsanitize=address,undefined: no out-of-range shift, no overflow it does not mean"""
-    assert "runtime error" not in host_check(tmp_path, "ip_host_check_san", ["-O1", "-g", "-fsanitize=address,undefined",
-                                                                            "-fno-sanitize-recover=undefined"])
+    assert "runtime error" not in host_check(tmp_path, "ip_host_check.cc", "ip_host_check_san", ("-w",) + SANITIZE)
 
 
 # ---- the C++ mirror ----------------------------------------------------------------------------------------------------------
-def ip_binary(name="test_ip_api", flags=("-O2",)):
-    """tests/cxx/test_ip_api.cc compiled against the mirror and the libraries (build() leaves it in place; rebuilt here when stale)"""
-    src, exe = os.path.join(CXX, "test_ip_api.cc"), os.path.join(CXX, "_build", name)
-    lib = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd")
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(_newest_header(), os.path.getmtime(src)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        b = subprocess.run(["g++", "-std=c++20", *flags, "-Wall", "-Wextra", "-Wno-unknown-pragmas", f"-I{ROOT}/include", "-o", exe, src,
-                            f"-L{lib}", "-lscl_hip_ip", "-lscl_hip_hm", "-lscl_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"],
-                           capture_output=True, text=True)
-        assert b.returncode == 0, b.stderr[-4000:]
-    return exe
-
-
 def test_the_mirror_prints_the_fixture():
     """the mirror's ss::shamirSecretShare on its util::PRG in the fixture's order, the local step through ip_dot_one
     (detail/ip.hpp), the open and the finish: what it prints is the fixture (exit status 0: every z is the inner product)"""
-    r = subprocess.run([ip_binary(), "--host"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert json.loads(r.stdout) == golden()
-    needed = subprocess.run(["readelf", "-d", ip_binary()], capture_output=True, text=True, check=True).stdout
-    assert "libscl_hip_ip.so" in needed and "libscl_hip.so" in needed
+    r = mirror_host_output("ip")
+    assert json.loads(r.stdout) == golden("ip")
+    dynamic = needed(mirror_binary("ip"))
+    assert "libscl_hip_ip.so" in dynamic and "libscl_hip.so" in dynamic

@@ -1,94 +1,13 @@
 """Merkle commitments, the host half: the C++ mirror's util::Sha256 / Bitmap / MerkleProof / MerkleTree
 (tests/cxx/test_merkle_api.cc) against hashlib and against trees the REFERENCE hashed (tests/golden/golden_merkle.json), the
-Python model of the reference's tree shape that checks the kernels in tests/test_gpu_merkle.py, and the new corner of the ABI."""
+Python model of the reference's tree shape (tests/merkle_model.py) that checks the kernels in tests/test_gpu_merkle.py, and the new corner of the ABI."""
 import ctypes as C
-import hashlib
-import json
 import os
 import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CXX = os.path.join(ROOT, "tests", "cxx")
-GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_merkle.json")
-ELEMENT_BYTES = {"Mersenne61": 8, "Mersenne127": 16, "Secp256k1Scalar": 32, "Secp256k1Field": 32}
-SHA_LENGTHS = [0, 3, 55, 56, 63, 64, 65, 119, 120, 300]
-
-
-def sha(b: bytes) -> bytes:
-    return hashlib.sha256(b).digest()
-
-
-# ---- the model: the reference's tree (include/scl/util/merkle.h:74-162) over hashlib ---------------------------------------
-# A level keeps its real node count; "repeat the last digest" (the leaf level when odd -- one leaf included -- and every later
-# level of odd size greater than one) is the right child's index clamped to the last node.
-def model_levels(leaf_digests):
-    """[level 0 = the leaf digests, level 1, .., [root]]"""
-    levels = [list(leaf_digests)]
-    while True:
-        cur = levels[-1]
-        levels.append([sha(cur[2 * j] + cur[min(2 * j + 1, len(cur) - 1)]) for j in range((len(cur) + 1) // 2)])
-        if len(levels[-1]) == 1:
-            return levels
-
-
-def model_path(levels, index):
-    """the sibling at every level below the root; direction[l] = bit l of the index"""
-    return [lv[min((index >> l) ^ 1, len(lv) - 1)] for l, lv in enumerate(levels[:-1])]
-
-
-def model_verify(leaf_digest, index, path, root):
-    d = leaf_digest
-    for l, s in enumerate(path):
-        d = sha(s + d) if (index >> l) & 1 else sha(d + s)
-    return d == root
-
-
-def model_tree_bytes(leaf_digests, L, T):
-    """scl_hip_merkle_build's buffer for T trees of L leaves, leaf digests laid out [leaf][tree]"""
-    per_tree = [model_levels([leaf_digests[j * T + t] for j in range(L)]) for t in range(T)]
-    return b"".join(per_tree[t][l][j] for l in range(len(per_tree[0])) for j in range(len(per_tree[0][l])) for t in range(T))
-
-
-def golden():
-    with open(GOLDEN) as fh:
-        return json.load(fh)["fields"]
-
-
-def golden_leaves(field, case):
-    raw, nb = bytes.fromhex(case["leaves"]), ELEMENT_BYTES[field]
-    assert len(raw) == case["L"] * nb
-    return [raw[i * nb:(i + 1) * nb] for i in range(case["L"])]
-
-
-def merkle_binary():
-    """tests/cxx/test_merkle_api.cc compiled against the mirror (build() leaves it in place; rebuilt here when stale)"""
-    src, exe = os.path.join(CXX, "test_merkle_api.cc"), os.path.join(CXX, "_build", "test_merkle_api")
-    lib = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd")
-    newest = max(os.path.getmtime(os.path.join(d, f)) for d, _, fs in os.walk(os.path.join(ROOT, "include")) for f in fs)
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(newest, os.path.getmtime(src)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        b = subprocess.run(["g++", "-std=c++20", "-O2", "-Wall", "-Wextra", "-Wno-unknown-pragmas", f"-I{ROOT}/include", "-o", exe, src,
-                            f"-L{lib}", "-lscl_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
-        assert b.returncode == 0, b.stderr[-4000:]
-    return exe
-
-
-def write_cases(path, sizes=None):
-    """the cases file of test_merkle_api: hashlib digests and the reference's trees"""
-    lines = []
-    for n in SHA_LENGTHS:
-        msg = bytes((7 * i + n) & 0xFF for i in range(n))
-        for split in sorted({0, n // 3, n}):
-            lines.append(f"sha {msg.hex() or '-'} {split} {sha(msg).hex()}")
-    lines.append(f"sha {b'abc'.hex()} 1 {sha(b'abc').hex()}")
-    for field, cases in golden().items():
-        for c in cases:
-            if sizes is None or c["L"] in sizes:
-                lines.append(f"tree {field} {c['L']} {c['leaves']} {c['root']} {c['index']} {c['proof_image']}")
-    with open(path, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
-    return len(lines)
+from cxx_support import ROOT, mirror_binary
+from merkle_model import ELEMENT_BYTES, golden, golden_leaves, model_levels, model_path, model_tree_bytes, model_verify, sha, write_cases
 
 
 def test_model_reproduces_the_reference_trees():
@@ -120,7 +39,7 @@ def test_cxx_mirror_hashes_and_proves_like_hashlib_and_the_reference(tmp_path):
     test_merkle.cc with Sha256, and every fixture tree through MerkleTree::hash / prove / verify and the proof's Serializer"""
     cases = str(tmp_path / "cases.txt")
     n = write_cases(cases)
-    r = subprocess.run([merkle_binary(), cases], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([mirror_binary("merkle"), cases], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert f"{n - 24} sha cases, 24 trees" in r.stdout and " 0 failures" in r.stdout, r.stdout
 

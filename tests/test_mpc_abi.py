@@ -2,18 +2,15 @@
 include/scl_hip_mpc.h, the binding takes its ctypes prototypes from that header, and every error the header promises is decided
 on the host, before a launch -- so each is reachable here, without a device, with pointers that are never dereferenced."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
 import oracle_lib as O
+from abi_support import (ERR_BAD_ARG, ERR_NO_DEVICE, ERR_SIZE_MISMATCH, OK, MPC, check_engine_is_only_dependency, check_exports, check_latch_rule,
+                         declared_symbols, expect)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "libscl_hip_mpc.so")
-OK, ERR_SIZE_MISMATCH, ERR_BAD_ARG, ERR_NO_DEVICE = 0, 1, 3, 5
 TAGS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD, O.Z2K(1), O.Z2K(64), O.Z2K(65), O.Z2K(128)]
+SYMBOLS = ["scl_mpc_abi_version", "scl_mpc_beaver_finish", "scl_mpc_beaver_mask", "scl_mpc_last_error"]
 BASE = 1 << 24      # a 16-byte aligned address that is never read: every case below ends before a launch
 
 
@@ -21,12 +18,6 @@ BASE = 1 << 24      # a 16-byte aligned address that is never read: every case b
 def mpc():
     import scl_amd.mpc
     return scl_amd.mpc
-
-
-def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "scl_hip_mpc.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_mpc_\w+)\s*\(", src)))
 
 
 def ptrs(k, step=1 << 20):
@@ -43,35 +34,20 @@ def finish_args(f, N=8, rows=1, ed_rows=0, z_stride=None, op_stride=None, p=None
     return (f, z, N if z_stride is None else z_stride, e, d, a, b, c, N if op_stride is None else op_stride, rows, ed_rows, N, None)
 
 
-def expect(mpc, rc, want):
-    msg = mpc.lib.scl_mpc_last_error()
-    assert rc == want, (rc, want, msg)
-    assert msg, "scl_mpc_last_error() is empty after a failure"
-
-
 def test_the_library_exports_the_header_and_nothing_else(mpc):
-    names = declared_symbols()
-    assert names == ["scl_mpc_abi_version", "scl_mpc_beaver_finish", "scl_mpc_beaver_mask", "scl_mpc_last_error"]
-    out = subprocess.run(["nm", "-D", "--defined-only", SO], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert exported == set(names), sorted(exported ^ set(names))
+    check_exports(MPC, SYMBOLS)
 
 
 def test_the_engine_is_its_only_project_dependency():
-    """linked against libscl_hip.so, found beside it ($ORIGIN); every undefined scl_* symbol is a prototype of scl_hip.h"""
-    dyn = subprocess.run(["readelf", "-d", SO], capture_output=True, text=True, check=True).stdout
-    assert "libscl_hip.so" in dyn and "$ORIGIN" in dyn, dyn
-    und = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout
-    used = sorted({ln.split()[-1].split("@")[0] for ln in und.splitlines() if "scl_" in ln})
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(scl_hip_\w+)\s*\(", hdr))
-    assert used and set(used) <= declared, used
+    """linked against libscl_hip.so, found beside it ($ORIGIN), and not against the other extension libraries; every undefined
+    scl_* symbol is a prototype of scl_hip.h"""
+    check_engine_is_only_dependency(MPC)
 
 
 def test_version_and_prototypes_come_from_the_header(mpc):
     assert mpc.lib.scl_mpc_abi_version() == 1
-    assert mpc._NPROTO == len(declared_symbols())
-    for name in declared_symbols():
+    assert mpc._NPROTO == len(declared_symbols(MPC))
+    for name in declared_symbols(MPC):
         assert getattr(mpc.lib, name).argtypes is not None, name
     assert mpc.lib.scl_mpc_last_error.restype is C.c_char_p
     m, f = mpc.lib.scl_mpc_beaver_mask.argtypes, mpc.lib.scl_mpc_beaver_finish.argtypes
@@ -107,40 +83,40 @@ def test_null_and_misaligned_pointers(mpc, f):
     for k in range(5):
         p = ptrs(5)
         p[k] = None
-        expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, p=p)), ERR_BAD_ARG)
         assert b"NULL" in lib.scl_mpc_last_error()
         p = ptrs(5)
         p[k] += off
-        expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, p=p)), ERR_BAD_ARG)
         assert b"aligned" in lib.scl_mpc_last_error()
     for k in range(6):
         p = ptrs(6)
         p[k] = None
-        expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, p=p)), ERR_BAD_ARG)
         assert b"NULL" in lib.scl_mpc_last_error()
         p = ptrs(6)
         p[k] += off
-        expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, p=p)), ERR_BAD_ARG)
         assert b"aligned" in lib.scl_mpc_last_error()
 
 
 @pytest.mark.parametrize("f", TAGS)
 def test_strides_and_ed_rows(mpc, f):
     lib = mpc.lib
-    expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=3, de_stride=7)), ERR_SIZE_MISMATCH)
-    expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=3, op_stride=7)), ERR_SIZE_MISMATCH)
-    expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=1, de_stride=0)), ERR_SIZE_MISMATCH)
-    expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, z_stride=7)), ERR_SIZE_MISMATCH)
-    expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, op_stride=7)), ERR_SIZE_MISMATCH)
-    expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, ed_rows=4)), ERR_BAD_ARG)
+    expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=3, de_stride=7)), ERR_SIZE_MISMATCH)
+    expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=3, op_stride=7)), ERR_SIZE_MISMATCH)
+    expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=1, de_stride=0)), ERR_SIZE_MISMATCH)
+    expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, z_stride=7)), ERR_SIZE_MISMATCH)
+    expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, op_stride=7)), ERR_SIZE_MISMATCH)
+    expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, ed_rows=4)), ERR_BAD_ARG)
     assert b"ed_rows" in lib.scl_mpc_last_error()
 
 
 @pytest.mark.parametrize("tag", [-1, 6, 0x100, 0x100 + 129, 0x7fffffff])
 def test_unknown_tags(mpc, tag):
-    expect(mpc, mpc.lib.scl_mpc_beaver_mask(*mask_args(tag)), ERR_BAD_ARG)
+    expect(MPC, mpc.lib.scl_mpc_beaver_mask(*mask_args(tag)), ERR_BAD_ARG)
     assert b"unknown field tag" in mpc.lib.scl_mpc_last_error()
-    expect(mpc, mpc.lib.scl_mpc_beaver_finish(*finish_args(tag)), ERR_BAD_ARG)
+    expect(MPC, mpc.lib.scl_mpc_beaver_finish(*finish_args(tag)), ERR_BAD_ARG)
     assert b"unknown field tag" in mpc.lib.scl_mpc_last_error()
 
 
@@ -151,19 +127,19 @@ def test_overlaps(mpc, f):
     for k in range(1, 5):
         p = ptrs(5)
         p[k] = p[0] + (2 * rows - 1) * N * esz          # the operand starts inside the last row of de
-        expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG)
         assert b"overlaps" in lib.scl_mpc_last_error()
     for k in (3, 4, 5):
         p = ptrs(6)
         p[0] = p[k] + esz                                # one element into a, b or c
-        expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG)
         p = ptrs(6)
         p[0] = p[k]                                      # exactly a, b or c, but at another stride
-        expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=N, rows=rows, z_stride=N + 2, op_stride=N, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=N, rows=rows, z_stride=N + 2, op_stride=N, p=p)), ERR_BAD_ARG)
     for k in (1, 2):
         p = ptrs(6)
         p[k] = p[0] + (rows - 1) * N * esz               # e or d inside the last row of z
-        expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG)
+        expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=N, rows=rows, p=p)), ERR_BAD_ARG)
         assert b"e or d" in lib.scl_mpc_last_error()
 
 
@@ -176,36 +152,15 @@ def test_a_well_formed_call_needs_a_device(mpc, f):
     if torch.cuda.is_available():
         pytest.skip("GPU present: these addresses must not reach a kernel")
     lib = mpc.lib
-    expect(mpc, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=3, de_stride=9, op_stride=11)), ERR_NO_DEVICE)
-    expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, ed_rows=3, z_stride=9, op_stride=11)), ERR_NO_DEVICE)
+    expect(MPC, lib.scl_mpc_beaver_mask(*mask_args(f, N=8, rows=3, de_stride=9, op_stride=11)), ERR_NO_DEVICE)
+    expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, ed_rows=3, z_stride=9, op_stride=11)), ERR_NO_DEVICE)
     p = ptrs(6)
     p[0] = p[3]
-    expect(mpc, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, ed_rows=1, z_stride=10, op_stride=10, p=p)), ERR_NO_DEVICE)
+    expect(MPC, lib.scl_mpc_beaver_finish(*finish_args(f, N=8, rows=3, ed_rows=1, z_stride=10, op_stride=10, p=p)), ERR_NO_DEVICE)
 
 
 def test_mont128_honours_the_latch_rule(mpc):
     """scl_hip_mont128_set_prime's rule reaches the extension: a worker whose latched default went stale is refused (the engine's
     own check and message) until it re-latches; the main thread, which set its own modulus, is not disturbed"""
-    from concurrent.futures import ThreadPoolExecutor
-    import scl_amd as scl
-    p0, p1 = 2 ** 128 - 159, 2 ** 127 - 1
-    bad_ed = finish_args(O.MONT128, rows=1, ed_rows=2)        # a call that ends at ed_rows > rows when the modulus is in order
-
-    def call():
-        rc = mpc.lib.scl_mpc_beaver_finish(*bad_ed)
-        return rc, mpc.lib.scl_mpc_last_error()
-    try:
-        scl.set_mont128_prime(p0)
-        with ThreadPoolExecutor(max_workers=1) as worker:
-            assert worker.submit(scl.mont128_prime).result() == p0     # the worker latches the default
-            rc, msg = worker.submit(call).result()
-            assert rc == ERR_BAD_ARG and b"ed_rows" in msg
-            scl.set_mont128_prime(p1)                                  # the main thread moves the default
-            rc, msg = worker.submit(call).result()
-            assert rc == ERR_BAD_ARG and b"latched" in msg
-            assert call()[1].find(b"ed_rows") >= 0                     # the main thread goes on
-            worker.submit(scl.mont128_relatch).result()
-            rc, msg = worker.submit(call).result()
-            assert rc == ERR_BAD_ARG and b"ed_rows" in msg
-    finally:
-        scl.set_mont128_prime(p0)
+    # a call that ends at ed_rows > rows when the modulus is in order
+    check_latch_rule(MPC, [(mpc.lib.scl_mpc_beaver_finish, finish_args(O.MONT128, rows=1, ed_rows=2), b"ed_rows", ERR_BAD_ARG)])

@@ -1,101 +1,16 @@
 """Pedersen VSS, the host half: ss::pedersen* of the C++ mirror (tests/cxx/test_pedersen_api.cc) against what the REFERENCE
-computed (tests/golden/golden_pedersen.json), and the big-integer Python model of tests/test_feldman_host.py, extended with
+computed (tests/golden/golden_pedersen.json), and the big-integer Python model of tests/secp256k1_model.py with its
 pedersen_verify, which pins the same fixture by something that is neither the reference nor this code.  The model also checks
 the kernels in tests/test_gpu_pedersen.py."""
-import functools
-import json
-import os
 import subprocess
 
-from test_feldman_host import CXX, G, Q, ROOT, ec_add, ec_from_image, ec_image, ec_mul, lagrange
+from cxx_support import mirror_binary
+from secp256k1_model import (G, Q, ec_add, ec_from_image, ec_image, ec_mul, every_run, matrix_of, pedersen_commitment, pedersen_verify, run_commitments,
+                             run_pairs, scalar_of)
+from secp256k1_model import pedersen_golden as golden
+from secp256k1_model import write_pedersen_cases as write_cases
 
-GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_pedersen.json")
 TAMPERED = ["share_plus_1", "randomness_plus_1", "commitment_0_is_G", "last_share_at_index_n_minus_1", "h_is_43G"]
-
-
-def pedersen_commitment(share: int, rand: int, h):
-    return ec_add(ec_mul(share, G), ec_mul(rand, h))
-
-
-def pedersen_verify(share: int, rand: int, commitments, index: int, h) -> bool:
-    """pedersen.h:178-207 without its shortcut: at an index below commitments.size() the basis is a unit vector"""
-    v = None
-    for l, c in zip(lagrange(range(len(commitments)), index), commitments):
-        v = ec_add(v, ec_mul(l, c))
-    return v == pedersen_commitment(share, rand, h)
-
-
-@functools.lru_cache(maxsize=None)
-def golden():
-    with open(GOLDEN) as fh:
-        return json.load(fh)["data"]
-
-
-def scalar_of(hex32: str) -> int:
-    assert len(hex32) == 64
-    return int(hex32, 16)
-
-
-def run_pairs(run):
-    """[(share, randomness)] per party"""
-    raw = run["shares"]
-    assert len(raw) == 128 * run["n"]
-    return [(int(raw[128 * i:128 * i + 64], 16), int(raw[128 * i + 64:128 * i + 128], 16)) for i in range(run["n"])]
-
-
-def run_commitments(run):
-    return [ec_from_image(bytes.fromhex(c)) for c in run["commitments"]]
-
-
-def every_run():
-    d = golden()
-    return d["runs"] + [d["run5"]] + d["hom_runs"] + d["apply"]["sharings"]
-
-
-def matrix_of(applied):
-    raw, rows, cols = applied["matrix"], applied["rows"], applied["cols"]
-    assert len(raw) == 64 * rows * cols
-    return [[int(raw[64 * (i * cols + k):64 * (i * cols + k + 1)], 16) for k in range(cols)] for i in range(rows)]
-
-
-def pedersen_binary():
-    """tests/cxx/test_pedersen_api.cc compiled against the mirror (build() leaves it in place; rebuilt here when stale)"""
-    src, exe = os.path.join(CXX, "test_pedersen_api.cc"), os.path.join(CXX, "_build", "test_pedersen_api")
-    lib = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd")
-    newest = max(os.path.getmtime(os.path.join(d, f)) for d, _, fs in os.walk(os.path.join(ROOT, "include")) for f in fs)
-    if not os.path.exists(exe) or os.path.getmtime(exe) < max(newest, os.path.getmtime(src)):
-        os.makedirs(os.path.dirname(exe), exist_ok=True)
-        b = subprocess.run(["g++", "-std=c++20", "-O2", "-Wall", "-Wextra", "-Wno-unknown-pragmas", f"-I{ROOT}/include", "-o", exe, src,
-                            f"-L{lib}", "-lscl_hip", f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True)
-        assert b.returncode == 0, b.stderr[-4000:]
-    return exe
-
-
-def write_cases(path):
-    """the fixture as lines for test_pedersen_api (its header has the grammar); a space in a seed is a '+'"""
-    d = golden()
-    lines = [f"h {d['h']} {d['h_wrong']}"]
-
-    def run_line(r):
-        return (f"run {r['overload']} {r['secret']} {r['randomness']} {r['t']} {r['n']} {r['counter0']} {r['shares']} "
-                f"{','.join(r['commitments'])}")
-
-    for r in d["runs"] + [d["run5"]]:
-        lines += ["prg " + r["seed"].replace(" ", "+"), run_line(r)]
-    lines.append("prg " + d["hom_runs"][0]["seed"].replace(" ", "+"))
-    lines += [run_line(r) for r in d["hom_runs"]]
-    lines.append(f"hom {d['hom']['shares']} {','.join(d['hom']['commitments'])} {d['hom']['sum_secret']} {d['hom']['sum_randomness']}")
-    lines.append("prg " + d["apply"]["sharings"][0]["seed"].replace(" ", "+"))
-    for r in d["apply"]["sharings"]:
-        lines += ["draw " + r["secret"], run_line(r)]
-    for key in ("vandermonde", "identity"):
-        a = d["apply"][key]
-        for j, party in enumerate(a["out"]):
-            for i, o in enumerate(party):
-                lines.append(f"apply {key} {j} {i} {o['share']} {','.join(o['commitments'])}")
-    with open(path, "w") as fh:
-        fh.write("\n".join(lines) + "\n")
-    return len(lines)
 
 
 def test_model_reproduces_the_reference_fixture():
@@ -164,6 +79,6 @@ def test_cxx_mirror_computes_what_the_reference_computed(tmp_path):
     verdicts -- through ss::pedersen* of the mirror"""
     cases = str(tmp_path / "cases.txt")
     n = write_cases(cases)
-    r = subprocess.run([pedersen_binary(), cases], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([mirror_binary("pedersen"), cases], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert f"{n} cases" in r.stdout and " 0 failures" in r.stdout, r.stdout

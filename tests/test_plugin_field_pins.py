@@ -21,7 +21,8 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
-from extremes import gf_inv, gf_mul  # the shift-xor model, shared with the extreme-operand tests
+from extremes import gf_inv, gf_mul, spec_mul  # the shift-xor model and the GCM specification's, shared with other tests
+from extremes import refl as _refl
 
 R = 1 << 128
 MASK = R - 1
@@ -184,10 +185,6 @@ def test_oracle_gf2_128_against_python_shift_xor(port):
 # A GCM block B (16 bytes, big-endian integer here) stands for sum_i b_i x^i with b_0 the MOST significant bit; an element of
 # this field is the integer with b_i at bit i.  Same field, same polynomial (GCM's R = 11100001 || 0^120 is 1 + x + x^2 + x^7):
 # element = the block's 128 bits reversed.
-def _refl(v: int) -> int:
-    return int(format(v, "0128b")[::-1], 2)
-
-
 GCM_CASES = [
     # test case 2: K = 0^128, P = 0^128, IV = 0^96
     {"H": 0x66e94bd4ef8a2c3b884cfa59ca342b2e, "blocks": [0x0388dace60b6a392f328c2b971b2fe78, 0x80],
@@ -199,17 +196,6 @@ GCM_CASES = [
      "X": [0x59ed3f2bb1a0aaa07c9f56c6a504647b, 0xb714c9048389afd9f9bc5c1d4378e052, 0x47400c6577b1ee8d8f40b2721e86ff10,
            0x4796cf49464704b5dd91f159bb1b7f95, 0x7f1b32b81b820d02614f8895ac1d4eac]},
 ]
-
-
-def spec_mul(X: int, Y: int) -> int:
-    """the multiplication of the GCM specification as it is written there (Algorithm 1: right shifts, R = e1 || 0^120) on
-    blocks as big-endian integers"""
-    Z, V = 0, X
-    for i in range(128):
-        if (Y >> (127 - i)) & 1:
-            Z ^= V
-        V = (V >> 1) ^ (0xe1 << 120) if V & 1 else V >> 1
-    return Z
 
 
 def _gcm_products():

@@ -3,19 +3,17 @@ include/scl_hip_prep.h, the binding takes its ctypes prototypes from that header
 and every error the header promises is decided on the host, before a launch -- so each is reachable here, without a device, with
 pointers that are never dereferenced."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import pytest
 
 import oracle_lib as O
+from abi_support import (ERR_BAD_ARG, ERR_NO_DEVICE, ERR_SIZE_MISMATCH, OK, PREP, check_engine_is_only_dependency, check_exports, check_latch_rule,
+                         declared_symbols, expect)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "libscl_hip_prep.so")
-OK, ERR_SIZE_MISMATCH, ERR_BAD_ARG, ERR_NO_DEVICE = 0, 1, 3, 5
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 RINGS = [O.Z2K(1), O.Z2K(64), O.Z2K(65), O.Z2K(128)]
+SYMBOLS = ["scl_prep_abi_version", "scl_prep_last_error", "scl_prep_triple_blocks", "scl_prep_triples_additive_prg",
+           "scl_prep_triples_scratch_bytes", "scl_prep_triples_shamir_prg"]
 BASE = 1 << 24      # a 16-byte aligned address that is never read: every case below ends before a launch
 SEED = b"prep abi"
 ADDITIVE, SHAMIR, TWO_PASS = 0, 1, 1
@@ -25,12 +23,6 @@ ADDITIVE, SHAMIR, TWO_PASS = 0, 1, 1
 def prep():
     import scl_amd.prep
     return scl_amd.prep
-
-
-def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "scl_hip_prep.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_prep_\w+)\s*\(", src)))
 
 
 def t_max(f):
@@ -52,39 +44,20 @@ def shamir_args(f, N=8, t=1, n=4, stride=None, p=None, counter0=0, scratch=BASE 
     return (f, a, b, c, N if stride is None else stride, N, t, n, SEED, len(SEED), counter0, scratch, flags, None)
 
 
-def expect(prep, rc, want, word=None):
-    msg = prep.lib.scl_prep_last_error()
-    assert rc == want, (rc, want, msg)
-    assert msg, "scl_prep_last_error() is empty after a failure"
-    if word:
-        assert word in msg, msg
-
-
 def test_the_library_exports_the_header_and_nothing_else(prep):
-    names = declared_symbols()
-    assert names == ["scl_prep_abi_version", "scl_prep_last_error", "scl_prep_triple_blocks", "scl_prep_triples_additive_prg",
-                     "scl_prep_triples_scratch_bytes", "scl_prep_triples_shamir_prg"]
-    out = subprocess.run(["nm", "-D", "--defined-only", SO], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert exported == set(names), sorted(exported ^ set(names))
+    check_exports(PREP, SYMBOLS)
 
 
 def test_the_engine_is_its_only_project_dependency():
-    """linked against libscl_hip.so, found beside it ($ORIGIN), and not against the protocol library; every undefined scl_* symbol
-    is a prototype of scl_hip.h"""
-    dyn = subprocess.run(["readelf", "-d", SO], capture_output=True, text=True, check=True).stdout
-    assert "libscl_hip.so" in dyn and "$ORIGIN" in dyn and "libscl_hip_mpc" not in dyn, dyn
-    und = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout
-    used = sorted({ln.split()[-1].split("@")[0] for ln in und.splitlines() if "scl_" in ln})
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(scl_hip_\w+)\s*\(", hdr))
-    assert used and set(used) <= declared, used
+    """linked against libscl_hip.so, found beside it ($ORIGIN), and not against the other extension libraries; every undefined
+    scl_* symbol is a prototype of scl_hip.h"""
+    check_engine_is_only_dependency(PREP)
 
 
 def test_version_and_prototypes_come_from_the_header(prep):
     assert prep.lib.scl_prep_abi_version() == 1
-    assert prep._NPROTO == len(declared_symbols()) == 6
-    for name in declared_symbols():
+    assert prep._NPROTO == len(declared_symbols(PREP)) == 6
+    for name in declared_symbols(PREP):
         assert getattr(prep.lib, name).argtypes is not None, name
     assert prep.lib.scl_prep_last_error.restype is C.c_char_p
     assert prep.lib.scl_prep_triple_blocks.restype is C.c_size_t and prep.lib.scl_prep_triples_scratch_bytes.restype is C.c_size_t
@@ -159,40 +132,40 @@ def test_null_and_misaligned_pointers(prep, f):
     for k in range(3):
         p = ptrs(3)
         p[k] = None
-        expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, p=p)), ERR_BAD_ARG, b"NULL")
+        expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, p=p)), ERR_BAD_ARG, b"NULL")
         if f in FIELDS:
-            expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, p=p)), ERR_BAD_ARG, b"NULL")
+            expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, p=p)), ERR_BAD_ARG, b"NULL")
         p = ptrs(3)
         p[k] += off
-        expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, p=p)), ERR_BAD_ARG, b"aligned")
+        expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, p=p)), ERR_BAD_ARG, b"aligned")
         if f in FIELDS:
-            expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, p=p)), ERR_BAD_ARG, b"aligned")
+            expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, p=p)), ERR_BAD_ARG, b"aligned")
 
 
 @pytest.mark.parametrize("f", FIELDS + RINGS)
 def test_strides_parties_and_flags(prep, f):
     lib = prep.lib
-    expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, N=8, stride=7)), ERR_SIZE_MISMATCH, b"stride < N")
+    expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, N=8, stride=7)), ERR_SIZE_MISMATCH, b"stride < N")
     for n in (0, 1):
-        expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, n=n)), ERR_BAD_ARG, b"n must be >= 2")
+        expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, n=n)), ERR_BAD_ARG, b"n must be >= 2")
     if f in FIELDS:
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=8, stride=7)), ERR_SIZE_MISMATCH, b"stride < N")
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, n=0)), ERR_BAD_ARG, b"n must be")
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, n=65536)), ERR_BAD_ARG, b"n must be")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=8, stride=7)), ERR_SIZE_MISMATCH, b"stride < N")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, n=0)), ERR_BAD_ARG, b"n must be")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, n=65536)), ERR_BAD_ARG, b"n must be")
         # a threshold at which the engine's share call would synchronise the stream is refused; the last one below it is not
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, t=t_max(f) + 1, n=200)), ERR_BAD_ARG, b"threshold t at most %d" % t_max(f))
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, t=65535, n=200)), ERR_BAD_ARG, b"threshold")
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, t=t_max(f), n=200, scratch=None)), ERR_BAD_ARG, b"scratch")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, t=t_max(f) + 1, n=200)), ERR_BAD_ARG, b"threshold t at most %d" % t_max(f))
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, t=65535, n=200)), ERR_BAD_ARG, b"threshold")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, t=t_max(f), n=200, scratch=None)), ERR_BAD_ARG, b"scratch")
         for flags in (2, 3, 0x80000000):
-            expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, flags=flags)), ERR_BAD_ARG, b"flags")
+            expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, flags=flags)), ERR_BAD_ARG, b"flags")
     else:       # Shamir shares over fields only, as scl_hip_shamir_share_prg
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f)), ERR_BAD_ARG, b"unknown field tag")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f)), ERR_BAD_ARG, b"unknown field tag")
 
 
 @pytest.mark.parametrize("tag", [-1, 6, 0x100, 0x100 + 129, 0x7fffffff])
 def test_unknown_tags(prep, tag):
-    expect(prep, prep.lib.scl_prep_triples_additive_prg(*additive_args(tag)), ERR_BAD_ARG, b"unknown field tag")
-    expect(prep, prep.lib.scl_prep_triples_shamir_prg(*shamir_args(tag)), ERR_BAD_ARG, b"unknown field tag")
+    expect(PREP, prep.lib.scl_prep_triples_additive_prg(*additive_args(tag)), ERR_BAD_ARG, b"unknown field tag")
+    expect(PREP, prep.lib.scl_prep_triples_shamir_prg(*shamir_args(tag)), ERR_BAD_ARG, b"unknown field tag")
 
 
 @pytest.mark.parametrize("f", [O.M61, O.SECP256K1_SCALAR])
@@ -202,18 +175,18 @@ def test_overlaps(prep, f):
     for i, j in ((0, 1), (0, 2), (1, 2), (1, 0), (2, 0), (2, 1)):
         p = ptrs(3)
         p[j] = p[i] + ((n - 1) * N + N - 1) * esz        # starts at the last element of the other matrix
-        expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, N=N, n=n, p=p)), ERR_BAD_ARG, b"overlap")
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, p=p)), ERR_BAD_ARG, b"overlap")
+        expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, N=N, n=n, p=p)), ERR_BAD_ARG, b"overlap")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, p=p)), ERR_BAD_ARG, b"overlap")
         p[j] = p[i] + n * N * esz                         # back to back is in order: the check AFTER the overlap check is met
         need = lib.scl_prep_triples_scratch_bytes(f, N, n, 9, 0)
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, t=9, p=p, scratch=None)), ERR_BAD_ARG, str(need).encode())
-        expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, N=N, n=n, p=p, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, t=9, p=p, scratch=None)), ERR_BAD_ARG, str(need).encode())
+        expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, N=N, n=n, p=p, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
     for k in range(3):
         p = ptrs(3)
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, t=9, p=p, scratch=p[k] + ((n * N - 1) * esz & ~15))), ERR_BAD_ARG,
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, t=9, p=p, scratch=p[k] + ((n * N - 1) * esz & ~15))), ERR_BAD_ARG,
                b"scratch overlaps")
         need = lib.scl_prep_triples_scratch_bytes(f, N, n, 9, 0)
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, t=9, p=p, scratch=p[k] - need + 16)), ERR_BAD_ARG,
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=N, n=n, t=9, p=p, scratch=p[k] - need + 16)), ERR_BAD_ARG,
                b"scratch overlaps")
 
 
@@ -223,17 +196,17 @@ def test_a_two_pass_case_without_scratch_names_the_size_it_needs(prep):
     for f, t, flags in cases:
         need = lib.scl_prep_triples_scratch_bytes(f, 257, 20, t, flags)
         assert need == (3 + 3 * t) * 257 * 8 * O.LIMBS[f]
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=257, t=t, n=20, scratch=None, flags=flags)), ERR_BAD_ARG,
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=257, t=t, n=20, scratch=None, flags=flags)), ERR_BAD_ARG,
                str(need).encode())
         assert b"scratch" in lib.scl_prep_last_error()
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=257, t=t, n=20, scratch=BASE + (8 << 20) + 8, flags=flags)), ERR_BAD_ARG,
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=257, t=t, n=20, scratch=BASE + (8 << 20) + 8, flags=flags)), ERR_BAD_ARG,
                b"aligned")
 
 
 def test_a_block_range_that_wraps_the_counter_is_refused(prep):
     lib = prep.lib
-    expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(O.M61, N=8, n=3, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
-    expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(O.M61, N=8, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
+    expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(O.M61, N=8, n=3, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
+    expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(O.M61, N=8, counter0=2 ** 64 - 8)), ERR_BAD_ARG, b"wraps")
 
 
 @pytest.mark.parametrize("f", FIELDS + RINGS)
@@ -245,37 +218,15 @@ def test_a_well_formed_call_needs_a_device(prep, f):
     if torch.cuda.is_available():
         pytest.skip("GPU present: these addresses must not reach a kernel")
     lib = prep.lib
-    expect(prep, lib.scl_prep_triples_additive_prg(*additive_args(f, N=8, n=3, stride=11, counter0=2 ** 32 - 5)), ERR_NO_DEVICE)
+    expect(PREP, lib.scl_prep_triples_additive_prg(*additive_args(f, N=8, n=3, stride=11, counter0=2 ** 32 - 5)), ERR_NO_DEVICE)
     if f in FIELDS:
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=8, t=3, n=10, stride=11)), ERR_NO_DEVICE)
-        expect(prep, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=8, t=9, n=20, stride=8, flags=TWO_PASS)), ERR_NO_DEVICE)
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=8, t=3, n=10, stride=11)), ERR_NO_DEVICE)
+        expect(PREP, lib.scl_prep_triples_shamir_prg(*shamir_args(f, N=8, t=9, n=20, stride=8, flags=TWO_PASS)), ERR_NO_DEVICE)
 
 
 def test_mont128_honours_the_latch_rule(prep):
     """scl_hip_mont128_set_prime's rule reaches the extension: a worker whose latched default went stale is refused (the engine's
     own check and message) until it re-latches; the main thread, which set its own modulus, is not disturbed"""
-    from concurrent.futures import ThreadPoolExecutor
-    import scl_amd as scl
-    p0, p1 = 2 ** 128 - 159, 2 ** 127 - 1
-    bad = [(prep.lib.scl_prep_triples_additive_prg, additive_args(O.MONT128, n=1), b"n must be >= 2"),     # calls that end at a later
-           (prep.lib.scl_prep_triples_shamir_prg, shamir_args(O.MONT128, flags=2), b"flags")]              # check when the modulus is in order
-
-    def call(fn, args):
-        rc = fn(*args)
-        return rc, prep.lib.scl_prep_last_error()
-    try:
-        for fn, args, word in bad:
-            scl.set_mont128_prime(p0)
-            with ThreadPoolExecutor(max_workers=1) as worker:
-                assert worker.submit(scl.mont128_prime).result() == p0     # the worker latches the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc == ERR_BAD_ARG and word in msg
-                scl.set_mont128_prime(p1)                                  # the main thread moves the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc == ERR_BAD_ARG and b"latched" in msg
-                assert word in call(fn, args)[1]                           # the main thread goes on
-                worker.submit(scl.mont128_relatch).result()
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc == ERR_BAD_ARG and word in msg
-    finally:
-        scl.set_mont128_prime(p0)
+    # calls that end at a later check when the modulus is in order
+    check_latch_rule(PREP, [(prep.lib.scl_prep_triples_additive_prg, additive_args(O.MONT128, n=1), b"n must be >= 2", ERR_BAD_ARG),
+                            (prep.lib.scl_prep_triples_shamir_prg, shamir_args(O.MONT128, flags=2), b"flags", ERR_BAD_ARG)])

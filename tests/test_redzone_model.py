@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import redzone as R
+from abi_support import ENGINE, declared_symbols
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -183,12 +184,6 @@ def test_several_strays_are_counted_and_grouped_by_window_and_side():
 
 
 # ---------------------------------------------------------------------------------------------- completeness
-def declared_symbols():
-    src = open(os.path.join(ROOT, "include", "scl_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_hip_\w+)\s*\(", src)))
-
-
 # The only entries that may be exempt: those that write no device memory through a caller's pointer.  Kept HERE, apart from the
 # EXEMPT dict of tests/test_gpu_redzones.py, so that moving an entry point from the table to the exemptions takes a change in two
 # files that says why.
@@ -212,7 +207,7 @@ MAY_BE_EXEMPT_PREFIXES = ("scl_hip_comm_", "scl_hip_open_")     # need RCCL rank
 
 def test_every_entry_point_is_a_table_row_or_exempt_with_a_reason():
     import test_gpu_redzones as G
-    names = declared_symbols()
+    names = declared_symbols(ENGINE)
     assert len(names) >= 98
     table, exempt = set(G.TABLE), set(G.EXEMPT)
     assert not table & exempt, sorted(table & exempt)

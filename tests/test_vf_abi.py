@@ -5,15 +5,13 @@ is reachable here, without a device, with pointers that are never dereferenced."
 import ctypes as C
 import os
 import re
-import subprocess
 
 import pytest
 
 import oracle_lib as O
+from abi_support import (ERR_BAD_ARG, ERR_NO_DEVICE, ERR_SIZE_MISMATCH, OK, PKG, VF, check_engine_is_only_dependency, check_exports,
+                         check_last_error_per_thread, check_latch_rule, declared_symbols, expect, header, reaches_the_device_check)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd", "libscl_hip_vf.so")
-OK, ERR_SIZE_MISMATCH, ERR_BAD_ARG, ERR_NO_DEVICE = 0, 1, 3, 5
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 RINGS = [O.Z2K(1), O.Z2K(64), O.Z2K(65), O.Z2K(128)]
 BASE = 1 << 24      # a 16-byte aligned address that is never read: every case below ends before a launch
@@ -28,15 +26,6 @@ SEED = b"vf abi"
 def vf():
     import scl_amd.vf
     return scl_amd.vf
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "scl_hip_vf.h")).read()
-
-
-def declared_symbols():
-    src = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    return sorted(set(re.findall(r"\b(scl_vf_\w+)\s*\(", src)))
 
 
 def esz(f):
@@ -70,47 +59,26 @@ def entry_points(vf):
     return [(vf.lib.scl_vf_combine_prg, prg_args, b"combine_prg"), (vf.lib.scl_vf_combine, rows_args, b"combine")]
 
 
-def expect(vf, rc, want, *words):
-    msg = vf.lib.scl_vf_last_error()
-    assert rc == want, (rc, want, msg)
-    assert msg, "scl_vf_last_error() is empty after a failure"
-    for w in words:
-        assert w in msg, msg
-
-
 def test_the_library_exports_the_header_and_nothing_else(vf):
-    names = declared_symbols()
-    assert names == SYMBOLS
-    out = subprocess.run(["nm", "-D", "--defined-only", SO], capture_output=True, text=True, check=True).stdout
-    exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    assert exported == set(names), sorted(exported ^ set(names))
-    listed = re.findall(r"^\s+(scl_vf_\w+);", open(os.path.join(ROOT, "secure-computation-library_amd", "csrc", "exports_vf.map")).read(), flags=re.M)
-    assert sorted(listed) == names
+    check_exports(VF, SYMBOLS)
 
 
 def test_the_engine_is_its_only_project_dependency():
     """linked against libscl_hip.so, found beside it ($ORIGIN), and not against the other extension libraries; every undefined
     scl_* symbol is a prototype of scl_hip.h"""
-    dyn = subprocess.run(["readelf", "-d", SO], capture_output=True, text=True, check=True).stdout
-    assert "libscl_hip.so" in dyn and "$ORIGIN" in dyn
-    assert not any(x in dyn for x in ("libscl_hip_mpc", "libscl_hip_prep", "libscl_hip_hm", "libscl_hip_ip")), dyn
-    und = subprocess.run(["nm", "-D", "--undefined-only", SO], capture_output=True, text=True, check=True).stdout
-    used = sorted({ln.split()[-1].split("@")[0] for ln in und.splitlines() if "scl_" in ln})
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scl_hip.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(scl_hip_\w+)\s*\(", hdr))
-    assert used and set(used) <= declared, used
+    check_engine_is_only_dependency(VF)
 
 
 def test_version_and_prototypes_come_from_the_header(vf):
     """the binding compares the version before it looks up another symbol (scl_amd/vf.py through the one loader, scl_amd/_abi.py)
     and types every prototype"""
-    assert vf.lib.scl_vf_abi_version() == 1 and re.search(r"#define\s+SCL_VF_ABI_VERSION\s+1\b", header())
-    pkg = os.path.join(ROOT, "secure-computation-library_amd", "scl_amd")
+    assert vf.lib.scl_vf_abi_version() == 1 and re.search(r"#define\s+SCL_VF_ABI_VERSION\s+1\b", header(VF))
+    pkg = os.path.join(PKG, "scl_amd")
     assert '_abi.declare(lib, _SO, "scl_hip_vf.h", "scl_vf_", "SCL_VF_ABI_VERSION"' in open(os.path.join(pkg, "vf.py")).read()
     src = open(os.path.join(pkg, "_abi.py")).read()
     assert src.index('getattr(lib, prefix + "abi_version")') < src.index("have = version()") < src.index("for m in re.finditer")
-    assert vf._NPROTO == len(declared_symbols()) == 7
-    for name in declared_symbols():
+    assert vf._NPROTO == len(declared_symbols(VF)) == 7
+    for name in declared_symbols(VF):
         assert getattr(vf.lib, name).argtypes is not None, name
     assert vf.lib.scl_vf_last_error.restype is C.c_char_p and vf.lib.scl_vf_launch_shape.restype is None
     assert vf.lib.scl_vf_coin_blocks.restype is C.c_size_t and vf.lib.scl_vf_scratch_bytes.restype is C.c_size_t
@@ -215,19 +183,19 @@ def test_repetitions_strides_scratch_and_the_counter(vf, f):
     lib = vf.lib
     for fn, args, who in entry_points(vf):
         for reps in (0, 5):
-            expect(vf, fn(*args(vf, f, reps=reps, out_stride=8, scratch_bytes=1 << 20)), ERR_BAD_ARG, who, b"reps must be at least 1 and at most 4")
-        expect(vf, fn(*args(vf, f, reps=3, out_stride=2)), ERR_SIZE_MISMATCH, who, b"out_stride < reps")
-        expect(vf, fn(*args(vf, f, op_stride=7)), ERR_SIZE_MISMATCH, who, b"op_stride < N")
+            expect(VF, fn(*args(vf, f, reps=reps, out_stride=8, scratch_bytes=1 << 20)), ERR_BAD_ARG, who, b"reps must be at least 1 and at most 4")
+        expect(VF, fn(*args(vf, f, reps=3, out_stride=2)), ERR_SIZE_MISMATCH, who, b"out_stride < reps")
+        expect(VF, fn(*args(vf, f, op_stride=7)), ERR_SIZE_MISMATCH, who, b"op_stride < N")
         n = need(vf, f, 3, 2, 8, PRG if fn is lib.scl_vf_combine_prg else 0)
-        expect(vf, fn(*args(vf, f, scratch_bytes=n - 1)), ERR_BAD_ARG, who, b"scratch_bytes", str(n).encode(), b"scl_vf_scratch_bytes")
-        expect(vf, fn(*args(vf, f, scratch_bytes=0)), ERR_BAD_ARG, who, b"scratch_bytes")
-        expect(vf, fn(*args(vf, f, rows=2 ** 61, scratch_bytes=1 << 20)), ERR_BAD_ARG, who, b"overflows")
-        expect(vf, fn(*args(vf, f, rows=2 ** 40, op_stride=2 ** 40, scratch_bytes=1 << 62)), ERR_BAD_ARG, who, b"overflows")
-    expect(vf, lib.scl_vf_combine(*rows_args(vf, f, rho_stride=7)), ERR_SIZE_MISMATCH, b"combine: rho_stride < N")
+        expect(VF, fn(*args(vf, f, scratch_bytes=n - 1)), ERR_BAD_ARG, who, b"scratch_bytes", str(n).encode(), b"scl_vf_scratch_bytes")
+        expect(VF, fn(*args(vf, f, scratch_bytes=0)), ERR_BAD_ARG, who, b"scratch_bytes")
+        expect(VF, fn(*args(vf, f, rows=2 ** 61, scratch_bytes=1 << 20)), ERR_BAD_ARG, who, b"overflows")
+        expect(VF, fn(*args(vf, f, rows=2 ** 40, op_stride=2 ** 40, scratch_bytes=1 << 62)), ERR_BAD_ARG, who, b"overflows")
+    expect(VF, lib.scl_vf_combine(*rows_args(vf, f, rho_stride=7)), ERR_SIZE_MISMATCH, b"combine: rho_stride < N")
     B = lib.scl_vf_coin_blocks(f, 8)
     for c0 in (2 ** 64 - 1, 2 ** 64 - 2 * B, 2 ** 64 - 2 * B - 64):
-        expect(vf, lib.scl_vf_combine_prg(*prg_args(vf, f, counter0=c0)), ERR_BAD_ARG, b"combine_prg: counter0 + reps * B wraps the 64-bit counter")
-    expect(vf, lib.scl_vf_combine_prg(*prg_args(vf, f, seed=None)[:9] + (None, 4) + prg_args(vf, f)[11:]), ERR_BAD_ARG, b"seed_host is NULL")
+        expect(VF, lib.scl_vf_combine_prg(*prg_args(vf, f, counter0=c0)), ERR_BAD_ARG, b"combine_prg: counter0 + reps * B wraps the 64-bit counter")
+    expect(VF, lib.scl_vf_combine_prg(*prg_args(vf, f, seed=None)[:9] + (None, 4) + prg_args(vf, f)[11:]), ERR_BAD_ARG, b"seed_host is NULL")
 
 
 @pytest.mark.parametrize("f", FIELDS)
@@ -241,15 +209,10 @@ def test_null_and_misaligned_pointers(vf, f):
             p = ptrs()
             p[i] = None
             if i != 2:
-                expect(vf, fn(*args(vf, f, p=p)), ERR_BAD_ARG, who, names[i], b"NULL")
+                expect(VF, fn(*args(vf, f, p=p)), ERR_BAD_ARG, who, names[i], b"NULL")
             p = ptrs()
             p[i] += 8 if i == 4 else off
-            expect(vf, fn(*args(vf, f, p=p)), ERR_BAD_ARG, who, names[i], b"aligned")
-
-
-def reaches_the_device_check(vf, rc):
-    """a call whose arguments are in order asks for a device next; with a GPU present these addresses must not get that far"""
-    assert rc == ERR_NO_DEVICE, (rc, vf.lib.scl_vf_last_error())
+            expect(VF, fn(*args(vf, f, p=p)), ERR_BAD_ARG, who, names[i], b"aligned")
 
 
 @pytest.mark.parametrize("f", [O.M61, O.SECP256K1_SCALAR])
@@ -267,16 +230,16 @@ def test_overlaps_and_the_allowed_aliases(vf, f):
                 for offset in (0, 16):
                     p = [out, x, y, rho, scratch]
                     p[k] = base + offset
-                    expect(vf, fn(*args(vf, f, N=N, rows=rows, reps=reps, p=p)), ERR_BAD_ARG, who, written + b" overlaps " + name)
+                    expect(VF, fn(*args(vf, f, N=N, rows=rows, reps=reps, p=p)), ERR_BAD_ARG, who, written + b" overlaps " + name)
             p = [out, x, y, rho, scratch]
             p[k] = out - (((reps if k == 3 else rows) * N - 1) * e & ~15)                # the input's last element runs into out
-            expect(vf, fn(*args(vf, f, N=N, rows=rows, reps=reps, p=p)), ERR_BAD_ARG, who, b"out_dev overlaps " + name)
+            expect(VF, fn(*args(vf, f, N=N, rows=rows, reps=reps, p=p)), ERR_BAD_ARG, who, b"out_dev overlaps " + name)
         for offset in (0, 16, -16):
-            expect(vf, fn(*args(vf, f, N=N, rows=rows, reps=reps, p=[out, x, y, rho, out + offset])), ERR_BAD_ARG, who, b"out_dev overlaps scratch_dev")
+            expect(VF, fn(*args(vf, f, N=N, rows=rows, reps=reps, p=[out, x, y, rho, out + offset])), ERR_BAD_ARG, who, b"out_dev overlaps scratch_dev")
         # a pitched out covers its gaps
-        expect(vf, fn(*args(vf, f, N=N, rows=rows, reps=reps, out_stride=64, p=[out, out + 16 * e, y, rho, scratch])), ERR_BAD_ARG, who, b"out_dev overlaps x_dev")
+        expect(VF, fn(*args(vf, f, N=N, rows=rows, reps=reps, out_stride=64, p=[out, out + 16 * e, y, rho, scratch])), ERR_BAD_ARG, who, b"out_dev overlaps x_dev")
         if no_gpu:
-            ok = lambda rc: reaches_the_device_check(vf, rc)
+            ok = lambda rc: reaches_the_device_check(VF, rc)
             ok(fn(*args(vf, f, N=N, rows=rows, reps=reps, p=[out, x, x, x, scratch])))              # inputs on one another: sum rho x^2
             ok(fn(*args(vf, f, N=N, rows=rows, reps=reps, p=[out, x, x + 16, x + 32, scratch])))
             ok(fn(*args(vf, f, N=N, rows=rows, reps=reps, p=[out, out + rows * reps * e, None, rho, scratch])))     # back to back, plain
@@ -293,50 +256,23 @@ def test_a_well_formed_call_needs_a_device(vf, f):
         pytest.skip("GPU present: these addresses must not reach a kernel")
     for fn, args, who in entry_points(vf):
         for reps in (1, 2, 3, 4):
-            expect(vf, fn(*args(vf, f, reps=reps, out_stride=reps + 3, op_stride=11)), ERR_NO_DEVICE)
-        expect(vf, fn(*args(vf, f, rows=1, N=1, reps=1)), ERR_NO_DEVICE)
+            expect(VF, fn(*args(vf, f, reps=reps, out_stride=reps + 3, op_stride=11)), ERR_NO_DEVICE)
+        expect(VF, fn(*args(vf, f, rows=1, N=1, reps=1)), ERR_NO_DEVICE)
         out, x, _, rho, scratch = ptrs()
-        expect(vf, fn(*args(vf, f, p=[out, x, None, rho, scratch])), ERR_NO_DEVICE)                # the plain form
-        expect(vf, fn(*args(vf, f, N=0, p=[out, None, None, None, scratch])), ERR_NO_DEVICE)       # the empty sum still writes zeros
-    expect(vf, vf.lib.scl_vf_combine_prg(*prg_args(vf, f, counter0=2 ** 64 - 2 ** 20)), ERR_NO_DEVICE)
+        expect(VF, fn(*args(vf, f, p=[out, x, None, rho, scratch])), ERR_NO_DEVICE)                # the plain form
+        expect(VF, fn(*args(vf, f, N=0, p=[out, None, None, None, scratch])), ERR_NO_DEVICE)       # the empty sum still writes zeros
+    expect(VF, vf.lib.scl_vf_combine_prg(*prg_args(vf, f, counter0=2 ** 64 - 2 ** 20)), ERR_NO_DEVICE)
 
 
 def test_mont128_honours_the_latch_rule(vf):
     """scl_hip_mont128_set_prime's rule reaches the extension: a worker whose latched default went stale is refused (the engine's
     own check and message) until it re-latches; the main thread, which set its own modulus, is not disturbed"""
-    from concurrent.futures import ThreadPoolExecutor
-    import scl_amd as scl
-    p0, p1 = 2 ** 128 - 159, 2 ** 127 - 1
-    lib = vf.lib
-    bad = [(lib.scl_vf_combine_prg, prg_args(vf, O.MONT128, reps=0, out_stride=4), b"reps"),           # calls that end at a later check
-           (lib.scl_vf_combine, rows_args(vf, O.MONT128, reps=0, out_stride=4), b"reps")]              # when the modulus is in order
-
-    def call(fn, args):
-        rc = fn(*args)
-        return rc, lib.scl_vf_last_error()
-    try:
-        for fn, args, word in bad:
-            scl.set_mont128_prime(p0)
-            with ThreadPoolExecutor(max_workers=1) as worker:
-                assert worker.submit(scl.mont128_prime).result() == p0     # the worker latches the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc != OK and word in msg
-                scl.set_mont128_prime(p1)                                  # the main thread moves the default
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc == ERR_BAD_ARG and b"latched" in msg
-                assert word in call(fn, args)[1]                           # the main thread goes on
-                worker.submit(scl.mont128_relatch).result()
-                rc, msg = worker.submit(call, fn, args).result()
-                assert rc != OK and word in msg
-    finally:
-        scl.set_mont128_prime(p0)
+    # calls that end at a later check when the modulus is in order
+    check_latch_rule(VF, [(vf.lib.scl_vf_combine_prg, prg_args(vf, O.MONT128, reps=0, out_stride=4), b"reps", ERR_BAD_ARG),
+                          (vf.lib.scl_vf_combine, rows_args(vf, O.MONT128, reps=0, out_stride=4), b"reps", ERR_BAD_ARG)])
 
 
 def test_the_last_error_is_per_thread(vf):
-    from concurrent.futures import ThreadPoolExecutor
     lib = vf.lib
-    lib.scl_vf_combine(*rows_args(vf, O.M61, op_stride=7))
-    with ThreadPoolExecutor(max_workers=1) as worker:
-        got = worker.submit(lambda: (lib.scl_vf_combine_prg(*prg_args(vf, O.M61, reps=0, out_stride=1)), lib.scl_vf_last_error())).result()
-        assert got[1].startswith(b"combine_prg: reps")
-    assert lib.scl_vf_last_error().startswith(b"combine: op_stride < N")
+    check_last_error_per_thread(VF, (lib.scl_vf_combine, rows_args(vf, O.M61, op_stride=7)), b"combine: op_stride < N",
+                                (lib.scl_vf_combine_prg, prg_args(vf, O.M61, reps=0, out_stride=1)), b"combine_prg: reps")
