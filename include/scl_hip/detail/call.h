@@ -41,7 +41,7 @@ inline void check(int status) {
   if (status != SCL_OK) raise(status);
 }
 
-/// a status of an extension library (libscl_hip_mpc.so, _prep, _hm, _ip, _vf) -> the same exceptions, with THAT library's
+/// a status of an extension library (libscl_hip_mpc.so, _prep, _hm, _ip, _vf, _rb) -> the same exceptions, with THAT library's
 /// diagnostic: `last_error` is its scl_X_last_error.  "Vec sizes mismatch" stays the reference's exception and text.
 inline void check(int status, const char* (*last_error)(void)) {
   if (status == SCL_OK) return;
