@@ -4,7 +4,7 @@
 //
 //   SCL_UNIT_ENGINE   a unit of libscl_hip.so (capi.hip, ec_, ecdsa_, pedersen_, hash_unit.hip, merkle_leaves.hip): the
 //                     diagnostics go to the engine's slot, sclhip_state::g_err, which capi.hip defines; the generic part only.
-//                     Without it the unit is an extension library beside the engine (libscl_hip_mpc / _prep / _hm / _ip / _vf / _rb):
+//                     Without it the unit is an extension library beside the engine (libscl_hip_mpc / _prep / _hm / _ip / _vf / _rb / _fx):
 //                     it owns its slot and, serving every field from one unit, takes the field part too, which wants
 //                     sclhip::BLOCK declared -- kernels.hpp's, or the unit's own (beaver_unit.hip).
 //   SCL_UNIT_AES      the unit launches four-table AES kernels: the AES part, which needs kernels.hpp.
@@ -107,7 +107,7 @@ size_t bpe_of(size_t limbs) { return limbs >= 2 ? limbs / 2 : 1; }  // AES block
 // device work -- the one place where a call of an extension library allocates, on the host and for Mont128 only).  That the
 // entry point keeps the check in front of its work is pinned from this side, once per library, by
 // test_mont128_honours_the_latch_rule of tests/test_mpc_abi.py, test_prep_abi.py, test_hm_abi.py, test_ip_abi.py,
-// test_vf_abi.py and test_rb_abi.py, which fail the day it does not.
+// test_vf_abi.py, test_rb_abi.py and test_fx_abi.py, which fail the day it does not.
 int mont_ctx(Mont128::Ctx& out) {
   uint64_t one_node[2];
   const int rc = scl_hip_lagrange_basis(SCL_MONT128, one_node, nullptr, 1, nullptr);
