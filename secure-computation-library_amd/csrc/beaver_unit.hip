@@ -2,87 +2,29 @@
 // libscl_hip_mpc.so (include/scl_hip_mpc.h), an extension library beside the engine.  One translation unit, all fields.
 //
 // Replaces the arithmetic around the open step of the reference's BeaverMul (test/scl/protocol/beaver.h:40-41 and 57-61) over
-// batches of secrets and parties.  The per-element functions are include/scl_hip/detail/beaver.hpp; the conventions are those of
-// the element-wise kernels of kernels.hpp: 256-lane blocks, one pack per lane, a grid-stride loop behind a capped grid,
-// streaming (non-temporal) 16-byte accesses -- two one-limb elements, one 16-byte element or half a 32-byte element each.  The
-// pack width of the one-limb fields is chosen on the host per call (16-byte aligned bases and even strides: two elements per
-// lane, else one); with two per lane an odd N leaves one element, which the lane after the last pack takes on its own, so a
-// call stays one launch.  No LDS, no scratch; the engine is reached through the prototypes of scl_hip.h only.
+// batches of secrets and parties.  The per-element functions are include/scl_hip/detail/beaver.hpp; the conventions are those
+// of the streaming kernels of every extension unit, csrc/unit_device.hpp: 256-lane blocks, one pack (kernels.hpp) per lane, a
+// grid-stride loop behind a capped grid, non-temporal 16-byte accesses, the pack width of the one-limb fields -- the rings
+// Z2k<K <= 64> among them -- chosen on the host per call, the odd last element taken by the lane after the last pair.  No LDS,
+// no scratch; the engine is reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/scl_hip_mpc.h"
 #include "../../include/scl_hip/detail/beaver.hpp"
+#include "kernels.hpp"
+#include "unit_device.hpp"
 
 namespace sclhip {
 namespace {
 
-constexpr int BLOCK = 256;
-typedef u64 u64x2 __attribute__((ext_vector_type(2)));
-
-// W consecutive elements at p (W = 2: one-limb fields only, p 16-byte aligned)
-template <class F, int W>
-struct Elems {
-  typename F::E v[W];
-};
-
-template <class F, int W>
-__device__ __forceinline__ Elems<F, W> load_elems(const u64* p) {
-  Elems<F, W> r;
-  if constexpr (F::LIMBS == 1 && W == 2) {
-    const u64x2 w = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(p));
-    r.v[0] = w.x;
-    r.v[1] = w.y;
-  } else if constexpr (F::LIMBS == 1) {
-    r.v[0] = __builtin_nontemporal_load(p);
-  } else if constexpr (F::LIMBS == 2) {
-    static_assert(W == 1, "16-byte elements: one per lane");
-    const u64x2 w = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(p));
-    r.v[0] = ((u128)w.y << 64) | w.x;
-  } else {
-    static_assert(W == 1 && F::LIMBS == 4, "32-byte elements: one per lane");
-    const u64x2 w0 = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(p));
-    const u64x2 w1 = __builtin_nontemporal_load(reinterpret_cast<const u64x2*>(p) + 1);
-    r.v[0].w[0] = w0.x;
-    r.v[0].w[1] = w0.y;
-    r.v[0].w[2] = w1.x;
-    r.v[0].w[3] = w1.y;
-  }
-  return r;
-}
-
-template <class F, int W>
-__device__ __forceinline__ void store_elems(u64* p, const Elems<F, W>& r) {
-  if constexpr (F::LIMBS == 1 && W == 2) {
-    u64x2 w;
-    w.x = r.v[0];
-    w.y = r.v[1];
-    __builtin_nontemporal_store(w, reinterpret_cast<u64x2*>(p));
-  } else if constexpr (F::LIMBS == 1) {
-    __builtin_nontemporal_store(r.v[0], p);
-  } else if constexpr (F::LIMBS == 2) {
-    u64x2 w;
-    w.x = (u64)r.v[0];
-    w.y = (u64)(r.v[0] >> 64);
-    __builtin_nontemporal_store(w, reinterpret_cast<u64x2*>(p));
-  } else {
-    u64x2 w0, w1;
-    w0.x = r.v[0].w[0];
-    w0.y = r.v[0].w[1];
-    w1.x = r.v[0].w[2];
-    w1.y = r.v[0].w[3];
-    __builtin_nontemporal_store(w0, reinterpret_cast<u64x2*>(p));
-    __builtin_nontemporal_store(w1, reinterpret_cast<u64x2*>(p) + 1);
-  }
-}
-
 // dst[i .. i + W) = x - a
 template <class F, int W>
 __device__ __forceinline__ void mask_at(const typename F::Ctx& ctx, u64* dst, const u64* x, const u64* a, size_t i) {
-  const Elems<F, W> xv = load_elems<F, W>(x + i * F::LIMBS), av = load_elems<F, W>(a + i * F::LIMBS);
-  Elems<F, W> r;
+  const Pack<F, W> xv = load_pack<F, W, true>(x + i * F::LIMBS), av = load_pack<F, W, true>(a + i * F::LIMBS);
+  Pack<F, W> r;
 #pragma unroll
   for (int v = 0; v < W; ++v) r.v[v] = beaver_mask_one<F>(ctx, xv.v[v], av.v[v]);
-  store_elems<F, W>(dst + i * F::LIMBS, r);
+  store_pack<F, W, true>(dst + i * F::LIMBS, r);
 }
 
 // Both subtractions of the mask in one launch: row blockIdx.y of e = x - a and of d = y - b (d lies `d_off` words past e).
@@ -96,16 +38,10 @@ __global__ __launch_bounds__(BLOCK) void k_beaver_mask(typename F::Ctx ctx, u64*
   y += in_row;
   a += in_row;
   b += in_row;
-  const size_t npacks = n / VEC, items = npacks + (VEC == 2 ? (n & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) {
-      mask_at<F, VEC>(ctx, e_out, x, a, q * VEC);
-      mask_at<F, VEC>(ctx, d_out, y, b, q * VEC);
-    } else {  // the odd element after the last pair
-      mask_at<F, 1>(ctx, e_out, x, a, n - 1);
-      mask_at<F, 1>(ctx, d_out, y, b, n - 1);
-    }
-  }
+  for_each_pack<VEC>(n, [&](auto w, size_t i) {
+    mask_at<F, w>(ctx, e_out, x, a, i);
+    mask_at<F, w>(ctx, d_out, y, b, i);
+  });
 }
 
 // z[r][i .. i + W) for every row r: e and d are loaded once, each row's a, b, c are read and its z written where they lie.
@@ -113,16 +49,16 @@ __global__ __launch_bounds__(BLOCK) void k_beaver_mask(typename F::Ctx ctx, u64*
 template <class F, int W>
 __device__ __forceinline__ void finish_at(const typename F::Ctx& ctx, u64* z, size_t z_stride, const u64* e, const u64* d, const u64* a,
                                           const u64* b, const u64* c, size_t op_stride, size_t rows, size_t ed_rows, size_t i) {
-  const Elems<F, W> ev = load_elems<F, W>(e + i * F::LIMBS), dv = load_elems<F, W>(d + i * F::LIMBS);
+  const Pack<F, W> ev = load_pack<F, W, true>(e + i * F::LIMBS), dv = load_pack<F, W, true>(d + i * F::LIMBS);
 #pragma unroll 1
   for (size_t r = 0; r < rows; ++r) {
     const size_t off = (r * op_stride + i) * F::LIMBS;
-    const Elems<F, W> av = load_elems<F, W>(a + off), bv = load_elems<F, W>(b + off), cv = load_elems<F, W>(c + off);
+    const Pack<F, W> av = load_pack<F, W, true>(a + off), bv = load_pack<F, W, true>(b + off), cv = load_pack<F, W, true>(c + off);
     const bool add_ed = r < ed_rows;  // the same in every lane
-    Elems<F, W> zv;
+    Pack<F, W> zv;
 #pragma unroll
     for (int v = 0; v < W; ++v) zv.v[v] = beaver_finish_one<F>(ctx, ev.v[v], dv.v[v], av.v[v], bv.v[v], cv.v[v], add_ed);
-    store_elems<F, W>(z + (r * z_stride + i) * F::LIMBS, zv);
+    store_pack<F, W, true>(z + (r * z_stride + i) * F::LIMBS, zv);
   }
 }
 
@@ -131,11 +67,7 @@ template <class F, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_beaver_finish(typename F::Ctx ctx, u64* z, size_t z_stride, const u64* e, const u64* d,
                                                          const u64* a, const u64* b, const u64* c, size_t op_stride, size_t rows,
                                                          size_t ed_rows, size_t n) {
-  const size_t npacks = n / VEC, items = npacks + (VEC == 2 ? (n & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) finish_at<F, VEC>(ctx, z, z_stride, e, d, a, b, c, op_stride, rows, ed_rows, q * VEC);
-    else finish_at<F, 1>(ctx, z, z_stride, e, d, a, b, c, op_stride, rows, ed_rows, n - 1);
-  }
+  for_each_pack<VEC>(n, [&](auto w, size_t i) { finish_at<F, w>(ctx, z, z_stride, e, d, a, b, c, op_stride, rows, ed_rows, i); });
 }
 
 }  // namespace
@@ -179,13 +111,8 @@ int scl_mpc_beaver_mask(int field, uint64_t* de, size_t de_stride, const uint64_
       const size_t r = rows - r0 < GRID_Y_MAX ? rows - r0 : GRID_Y_MAX;
       u64* out0 = de + r0 * de_stride * F::LIMBS;
       const size_t in0 = r0 * op_stride * F::LIMBS;
-      if (two)
-        hipLaunchKernelGGL((k_beaver_mask<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1)), (unsigned)r), dim3(BLOCK), 0,
-                           S(stream), ctx, out0, de_stride, d_off, x + in0, y + in0, a + in0, b + in0, op_stride, N);
-      else
-        hipLaunchKernelGGL((k_beaver_mask<F, 1>), dim3(grid_for(N), (unsigned)r), dim3(BLOCK), 0, S(stream), ctx, out0, de_stride,
-                           d_off, x + in0, y + in0, a + in0, b + in0, op_stride, N);
-      HIP_TRY(hipGetLastError());
+      PACK_LAUNCH((k_beaver_mask, F), two, dim3(grid_for_packs(two, N), (unsigned)r), S(stream), ctx, out0, de_stride, d_off, x + in0, y + in0,
+                  a + in0, b + in0, op_stride, N);
     }
     return SCL_OK;
   });
@@ -215,13 +142,8 @@ int scl_mpc_beaver_finish(int field, uint64_t* z, size_t z_stride, const uint64_
     if (overlap(out, span_of(e, 1, N, N, F::LIMBS)) || overlap(out, span_of(d, 1, N, N, F::LIMBS)))
       return fail(SCL_ERR_BAD_ARG, "beaver_finish: z overlaps e or d");
     if (const int rc = need_device()) return rc;
-    if (two_per_lane(F::LIMBS, {z, e, d, a, b, c}, {rows > 1 ? z_stride : 0, rows > 1 ? op_stride : 0}))
-      hipLaunchKernelGGL((k_beaver_finish<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1))), dim3(BLOCK), 0, S(stream), ctx, z,
-                         z_stride, e, d, a, b, c, op_stride, rows, ed_rows, N);
-    else
-      hipLaunchKernelGGL((k_beaver_finish<F, 1>), dim3(grid_for(N)), dim3(BLOCK), 0, S(stream), ctx, z, z_stride, e, d, a, b, c,
-                         op_stride, rows, ed_rows, N);
-    HIP_TRY(hipGetLastError());
+    const bool two = two_per_lane(F::LIMBS, {z, e, d, a, b, c}, {rows > 1 ? z_stride : 0, rows > 1 ? op_stride : 0});
+    PACK_LAUNCH((k_beaver_finish, F), two, dim3(grid_for_packs(two, N)), S(stream), ctx, z, z_stride, e, d, a, b, c, op_stride, rows, ed_rows, N);
     return SCL_OK;
   });
 }

@@ -11,20 +11,19 @@
 //                  canonical integer (one from_mont for the Montgomery fields), the limb-wise mask, the range check, the rows
 // The plane loop is rolled (B is a run-time value) in groups of FX_GROUP planes whose loads are issued before their arithmetic.
 // No LDS, no atomics, no allocation, no synchronisation.  256-lane blocks, grid-stride loops, 16-byte non-temporal accesses, the
-// odd last element of a Mersenne61 row taken by the lane after the last pair (the conventions of csrc/hm_unit.hip and
-// csrc/rb_unit.hip).  The engine is reached through the prototypes of scl_hip.h only.
+// odd last element of a Mersenne61 row taken by the lane after the last pair (the conventions of csrc/unit_device.hpp, whose
+// open_at is the opening).  The engine is reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/scl_hip_fx.h"
 #include "../../include/scl_hip/detail/fx.hpp"
 #include "kernels.hpp"
+#include "unit_device.hpp"
 
 namespace sclhip {
 namespace {
 
-constexpr int FX_GROUP = 4;      // planes whose loads are in flight together
-constexpr int FX_M_MAX = 64;     // shares an opening takes
-static_assert(FX_M_MAX <= (int)M61::ACC_TERMS, "the open of k_fx_finish never folds");
+constexpr int FX_GROUP = 4;  // planes whose loads are in flight together
 
 // The planes B - 1 .. 0 of columns [i, i + W) of one row: r into acc, and -- LOW -- the planes below `shift` into low.  `bits`
 // points at plane 0 of the row.  Lazy sums (fx_step): the caller canonicalises.
@@ -85,11 +84,7 @@ __global__ __launch_bounds__(BLOCK) void k_fx_compose(typename F::Ctx ctx, u64* 
                                                       size_t row_stride, int B, size_t N) {
   out += (size_t)blockIdx.y * out_stride * F::LIMBS;
   bits += (size_t)blockIdx.y * row_stride * F::LIMBS;
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) compose_at<F, VEC>(ctx, out, bits, plane_stride, B, q * VEC);
-    else compose_at<F, 1>(ctx, out, bits, plane_stride, B, N - 1);  // the odd element after the last pair
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) { compose_at<F, w>(ctx, out, bits, plane_stride, B, i); });
 }
 
 // a lane reads its x before it writes its c, so c may be x
@@ -117,38 +112,20 @@ __global__ __launch_bounds__(BLOCK) void k_fx_mask(typename F::Ctx ctx, FxMask<F
   rlow += (size_t)blockIdx.y * rlow_stride * F::LIMBS;
   x += (size_t)blockIdx.y * x_stride * F::LIMBS;
   bits += (size_t)blockIdx.y * row_stride * F::LIMBS;
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) mask_at<F, VEC>(ctx, prm, c, rlow, x, bits, plane_stride, B, shift, q * VEC);
-    else mask_at<F, 1>(ctx, prm, c, rlow, x, bits, plane_stride, B, shift, N - 1);
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) { mask_at<F, w>(ctx, prm, c, rlow, x, bits, plane_stride, B, shift, i); });
 }
-
-template <class F>
-struct FxLambda {  // kernel-argument table (2 KiB for the 32-byte fields)
-  typename F::E v[FX_M_MAX];
-};
 
 // y[r][i .. i + W) for every row r: the opened value once, its low bits and status, each row's x and r' read and its y written
 // where it lies (a lane reads its elements before it writes them, so y may be x or r')
 template <class F, int W>
 __device__ __forceinline__ void finish_at(const typename F::Ctx& ctx, const FxFinish<F>& prm, u64* y, size_t y_stride, unsigned char* status,
-                                          const u64* csh, size_t c_stride, const FxLambda<F>& lam, int m, const u64* x, size_t x_stride,
+                                          const u64* csh, size_t c_stride, const OpenTable<F>& lam, int m, const u64* x, size_t x_stride,
                                           const u64* rlow, size_t rlow_stride, size_t rows, size_t i) {
-  typename F::Acc acc[W];
-#pragma unroll
-  for (int v = 0; v < W; ++v) acc[v] = F::acc_zero();
-#pragma unroll 1
-  for (int j = 0; j < m; ++j) {  // m <= 64 <= every field's F::ACC_TERMS: no fold on the way
-    const Pack<F, W> cv = load_pack<F, W, true>(csh + ((size_t)j * c_stride + i) * F::LIMBS);
-    const typename F::E l = lam.v[j];
-#pragma unroll
-    for (int v = 0; v < W; ++v) F::mac(ctx, acc[v], l, cv.v[v]);
-  }
-  typename F::E cp[W];
+  typename F::E opened[W], cp[W];
+  open_at<F, W>(ctx, csh, c_stride, lam.v, m, i, opened);  // (the table where it lies: the kernel arguments)
   int st[W];
 #pragma unroll
-  for (int v = 0; v < W; ++v) cp[v] = fx_finish_col<F>(ctx, prm, F::acc_fold(ctx, acc[v]), st[v]);
+  for (int v = 0; v < W; ++v) cp[v] = fx_finish_col<F>(ctx, prm, opened[v], st[v]);
 #pragma unroll 1
   for (size_t r = 0; r < rows; ++r) {
     const Pack<F, W> xv = load_pack<F, W, true>(x + (r * x_stride + i) * F::LIMBS), lv = load_pack<F, W, true>(rlow + (r * rlow_stride + i) * F::LIMBS);
@@ -163,13 +140,11 @@ __device__ __forceinline__ void finish_at(const typename F::Ctx& ctx, const FxFi
 
 template <class F, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_fx_finish(typename F::Ctx ctx, FxFinish<F> prm, u64* y, size_t y_stride, unsigned char* status,
-                                                     const u64* csh, size_t c_stride, FxLambda<F> lam, int m, const u64* x, size_t x_stride,
+                                                     const u64* csh, size_t c_stride, OpenTable<F> lam, int m, const u64* x, size_t x_stride,
                                                      const u64* rlow, size_t rlow_stride, size_t rows, size_t N) {
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) finish_at<F, VEC>(ctx, prm, y, y_stride, status, csh, c_stride, lam, m, x, x_stride, rlow, rlow_stride, rows, q * VEC);
-    else finish_at<F, 1>(ctx, prm, y, y_stride, status, csh, c_stride, lam, m, x, x_stride, rlow, rlow_stride, rows, N - 1);
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) {
+    finish_at<F, w>(ctx, prm, y, y_stride, status, csh, c_stride, lam, m, x, x_stride, rlow, rlow_stride, rows, i);
+  });
 }
 
 }  // namespace
@@ -182,18 +157,8 @@ namespace {
 
 // the tags this library refuses, each with its reason; SCL_OK for the five prime fields
 int check_tag(const std::string& w, int field) {
-  if (field == SCL_GF2_128)
-    return fail(SCL_ERR_BAD_ARG, w + ": SCL_GF2_128 is refused: GF(2^128) has no integers below a prime, there is nothing to reduce modulo 2^shift");
-  if (is_ring(field))
-    return fail(SCL_ERR_BAD_ARG, w + ": a ring tag is refused: a ring Z2k is not a field, it has no 2^-shift and no Shamir sharing");
-  if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, w + ": unknown field tag");
-  return SCL_OK;
-}
-
-int check_ptr(const std::string& w, size_t L, const char* name, const void* p) {
-  if (!p) return fail(SCL_ERR_BAD_ARG, w + ": " + name + " is NULL");
-  if (reinterpret_cast<uintptr_t>(p) & (L == 1 ? 7 : 15)) return fail(SCL_ERR_BAD_ARG, w + ": " + name + (L == 1 ? " not 8-byte aligned" : " not 16-byte aligned"));
-  return SCL_OK;
+  return check_prime_field(w, field, "GF(2^128) has no integers below a prime, there is nothing to reduce modulo 2^shift",
+                           "a ring Z2k is not a field, it has no 2^-shift and no Shamir sharing");
 }
 
 // |p| - 2 of an accepted tag (`mont`: what mont_latch yielded)
@@ -206,18 +171,11 @@ size_t max_bits(int field, const Mont128::Ctx& mont) {
   }
 }
 
-// the planes as one operand: the elements from plane 0 of row 0 to the end of plane B - 1 of row rows - 1.  false: the extent
-// does not fit
-bool planes_extent(size_t plane_stride, size_t row_stride, size_t B, size_t rows, size_t N, size_t* extent) {
-  size_t a = 0, b = 0;
-  if (__builtin_mul_overflow(B - 1, plane_stride, &a) || __builtin_mul_overflow(rows - 1, row_stride, &b)) return false;
-  return !__builtin_add_overflow(a, b, &a) && !__builtin_add_overflow(a, N, extent);
-}
-
+// the planes as one operand (`extent`): the elements from plane 0 of row 0 to the end of plane B - 1 of row rows - 1
 int check_planes(const std::string& w, size_t plane_stride, size_t row_stride, size_t B, size_t rows, size_t N, size_t* extent) {
   if (B > 1 && plane_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, w + ": plane_stride < N");
   if (rows > 1 && row_stride < N) return fail(SCL_ERR_SIZE_MISMATCH, w + ": row_stride < N");
-  if (!planes_extent(plane_stride, row_stride, B, rows, N, extent)) return fail(SCL_ERR_BAD_ARG, w + ": the extent of bits_dev overflows");
+  if (!extent_of({{B, plane_stride}, {rows, row_stride}}, N, extent)) return fail(SCL_ERR_BAD_ARG, w + ": the extent of bits_dev overflows");
   return SCL_OK;
 }
 
@@ -262,13 +220,8 @@ int scl_fx_compose(int field, uint64_t* out_dev, size_t out_stride, const uint64
         const size_t nr = rows - r0 < GRID_Y_MAX ? rows - r0 : GRID_Y_MAX;
         uint64_t* o = out_dev + r0 * out_stride * L;
         const uint64_t* b = bits_dev + r0 * row_stride * L;
-        if (two)
-          hipLaunchKernelGGL((k_fx_compose<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1)), (unsigned)nr), dim3(BLOCK), 0, S(stream), ctx, o,
-                             out_stride, b, plane_stride, row_stride, (int)B, N);
-        else
-          hipLaunchKernelGGL((k_fx_compose<F, 1>), dim3(grid_for(N), (unsigned)nr), dim3(BLOCK), 0, S(stream), ctx, o, out_stride, b, plane_stride,
-                             row_stride, (int)B, N);
-        HIP_TRY(hipGetLastError());
+        PACK_LAUNCH((k_fx_compose, F), two, dim3(grid_for_packs(two, N), (unsigned)nr), S(stream), ctx, o, out_stride, b, plane_stride, row_stride,
+                    (int)B, N);
       }
       return SCL_OK;
     }
@@ -313,13 +266,8 @@ int scl_fx_trunc_mask(int field, uint64_t* c_dev, size_t c_stride, uint64_t* rlo
         const size_t nr = rows - r0 < GRID_Y_MAX ? rows - r0 : GRID_Y_MAX;
         uint64_t *c = c_dev + r0 * c_stride * L, *lo = rlow_dev + r0 * rlow_stride * L;
         const uint64_t *x = x_dev + r0 * x_stride * L, *b = bits_dev + r0 * row_stride * L;
-        if (two)
-          hipLaunchKernelGGL((k_fx_mask<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1)), (unsigned)nr), dim3(BLOCK), 0, S(stream), ctx, prm, c,
-                             c_stride, lo, rlow_stride, x, x_stride, b, plane_stride, row_stride, (int)B, (int)shift, N);
-        else
-          hipLaunchKernelGGL((k_fx_mask<F, 1>), dim3(grid_for(N), (unsigned)nr), dim3(BLOCK), 0, S(stream), ctx, prm, c, c_stride, lo, rlow_stride, x,
-                             x_stride, b, plane_stride, row_stride, (int)B, (int)shift, N);
-        HIP_TRY(hipGetLastError());
+        PACK_LAUNCH((k_fx_mask, F), two, dim3(grid_for_packs(two, N), (unsigned)nr), S(stream), ctx, prm, c, c_stride, lo, rlow_stride, x, x_stride, b,
+                    plane_stride, row_stride, (int)B, (int)shift, N);
       }
       return SCL_OK;
     }
@@ -338,7 +286,7 @@ int scl_fx_trunc_finish(int field, uint64_t* y_dev, size_t y_stride, unsigned ch
   if (shift == 0) return fail(SCL_ERR_BAD_ARG, w + ": shift == 0: there is nothing to truncate");
   if (shift >= B) return fail(SCL_ERR_BAD_ARG, w + ": shift >= B: shift is below k and k at most B");
   if (B > top) return fail(SCL_ERR_BAD_ARG, w + ": B > scl_fx_max_bits: B must be at most " + std::to_string(top) + " for this field (|p| - 2: the opened value stays below p)");
-  if (m == 0 || m > (size_t)FX_M_MAX)
+  if (m == 0 || m > (size_t)OPEN_M_MAX)
     return fail(SCL_ERR_BAD_ARG, w + ": m must be in 1..64 (lambda travels with the launch); beyond that open with scl_hip_shamir_recover and pass m = 1, lambda = {1}");
   if (const int rc = check_ptr(w, L, "y_dev", y_dev)) return rc;
   if (!status_dev) return fail(SCL_ERR_BAD_ARG, w + ": status_dev is NULL");
@@ -361,15 +309,9 @@ int scl_fx_trunc_finish(int field, uint64_t* y_dev, size_t y_stride, unsigned ch
     } else {
       if (const int rc = need_device()) return rc;
       const FxFinish<F> prm = fx_make_finish<F>(ctx, (int)shift, (int)B);
-      FxLambda<F> tab;
-      for (size_t j = 0; j < (size_t)FX_M_MAX; ++j) tab.v[j] = j < m ? F::ld(lambda_host + j * F::LIMBS) : F::zero();
-      if (two_per_lane(L, {y_dev, csh_dev, x_dev, rlow_dev}, {rows > 1 ? y_stride : 0, rows > 1 ? x_stride : 0, rows > 1 ? rlow_stride : 0, m > 1 ? c_stride : 0}))
-        hipLaunchKernelGGL((k_fx_finish<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1))), dim3(BLOCK), 0, S(stream), ctx, prm, y_dev, y_stride,
-                           status_dev, csh_dev, c_stride, tab, (int)m, x_dev, x_stride, rlow_dev, rlow_stride, rows, N);
-      else
-        hipLaunchKernelGGL((k_fx_finish<F, 1>), dim3(grid_for(N)), dim3(BLOCK), 0, S(stream), ctx, prm, y_dev, y_stride, status_dev, csh_dev, c_stride, tab,
-                           (int)m, x_dev, x_stride, rlow_dev, rlow_stride, rows, N);
-      HIP_TRY(hipGetLastError());
+      const bool two = two_per_lane(L, {y_dev, csh_dev, x_dev, rlow_dev}, {rows > 1 ? y_stride : 0, rows > 1 ? x_stride : 0, rows > 1 ? rlow_stride : 0, m > 1 ? c_stride : 0});
+      PACK_LAUNCH((k_fx_finish, F), two, dim3(grid_for_packs(two, N)), S(stream), ctx, prm, y_dev, y_stride, status_dev, csh_dev, c_stride,
+                  make_open_table<F>(lambda_host, m), (int)m, x_dev, x_stride, rlow_dev, rlow_stride, rows, N);
       return SCL_OK;
     }
   });

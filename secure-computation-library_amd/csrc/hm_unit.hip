@@ -6,7 +6,7 @@
 //   k_double_share_prg   one lane = one double sharing: r, then the degree-t and the degree-2t polynomial one after another (at
 //                        most 2t + 1 <= 7 coefficients live), the parties in a rolled loop, Horner at the small node i + 1;
 //                        one kernel per threshold 0..3, on the four-table AES of kernels.hpp as k_triples_shamir_prg
-//                        (csrc/triples_unit.hip, whose draw helpers are restated here)
+//                        (csrc/triples_unit.hip; the draws of both are csrc/prg_deal.hpp)
 //   k_double_coeff_rows  the first of two passes: r and the 3t coefficient rows into the caller's scratch; the engine's
 //                        explicit-coefficient scl_hip_shamir_share evaluates them (two calls)
 //   k_hm_apply           one lane = one column (Mersenne61: two), R output rows in lazy accumulators, the n input rows walked
@@ -15,7 +15,7 @@
 //                        m rows of M (whole in LDS) with one accumulator: in read once, out written once
 //   k_hm_mask            x y + r2, row blockIdx.y
 //   k_hm_finish          sum_j lambda_j dsh[j] once per column, minus each row of r; lambda staged in LDS from kernel arguments
-// The streaming kernels keep the conventions of csrc/beaver_unit.hip: 256-lane blocks, 16-byte non-temporal accesses, the pack
+// The streaming kernels keep the conventions of csrc/unit_device.hpp: 256-lane blocks, 16-byte non-temporal accesses, the pack
 // width of Mersenne61 chosen on the host per call, the odd last element taken by the lane after the last pair.  The engine is
 // reached through the prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
@@ -23,81 +23,13 @@
 #include "../../include/scl_hip_hm.h"
 #include "../../include/scl_hip/detail/hm.hpp"
 #include "kernels.hpp"
+#include "prg_deal.hpp"
+#include "unit_device.hpp"
 
 namespace sclhip {
 namespace {
 
-constexpr int FINISH_M_MAX = 64;
-static_assert(FINISH_M_MAX <= (int)M61::ACC_TERMS, "the open of k_hm_finish never folds");
-
 // ---- the dealer ------------------------------------------------------------------------------------------------------------
-template <class F>
-constexpr int bpe() {  // FF::random burns ceil(byteSize/16) blocks (ff.h:72-76)
-  return F::LIMBS >= 2 ? F::LIMBS / 2 : 1;
-}
-
-// one FF::random at block c0: a one-limb element is the first 8 bytes of its block
-template <class F>
-__device__ __forceinline__ typename F::E draw_elem(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64 c0) {
-  constexpr int BPE = bpe<F>();
-  u64 lo[BPE], hi[BPE];
-#pragma unroll
-  for (int b = 0; b < BPE; ++b) aes.block(key, c0 + b, lo[b], hi[b]);
-  if constexpr (F::LIMBS == 1) return F::from_le_word(ctx, lo[0]);
-  else return elem_from_blocks<F>(ctx, lo, hi);
-}
-
-// Blocks of one Vector::random(d+1) draw
-template <class F>
-__host__ __device__ constexpr u64 poly_blocks(u64 d) {
-  return ((d + 1) * (u64)(8 * F::LIMBS) + 15) / 16;
-}
-
-// coefficients 1..D of the polynomial whose Vector::random(D+1) draw starts at block p0 (element 0 is discarded, shamir.h:57):
-// one-limb fields hold elements 2j and 2j+1 in block j, wider ones element k in blocks k*BPE ..
-template <class F, int D>
-__device__ __forceinline__ void draw_poly(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64 p0,  // (by value)
-                                          typename F::E (&c)[D + 1]) {
-  if constexpr (F::LIMBS == 1) {
-#pragma unroll
-    for (int j = 0; 2 * j <= D; ++j) {
-      u64 lo, hi;
-      aes.block(key, p0 + j, lo, hi);
-      if (j > 0) c[2 * j] = F::from_le_word(ctx, lo);
-      if (2 * j + 1 <= D) c[2 * j + 1] = F::from_le_word(ctx, hi);
-    }
-  } else {
-    constexpr int BPE = bpe<F>();
-#pragma unroll
-    for (int k = 1; k <= D; ++k) {
-      u64 lo[BPE], hi[BPE];
-#pragma unroll
-      for (int b = 0; b < BPE; ++b) aes.block(key, p0 + (u64)k * BPE + b, lo[b], hi[b]);
-      c[k] = elem_from_blocks<F>(ctx, lo, hi);
-      // one coefficient's blocks at a time: left alone the compiler runs all D draws abreast and runs
-      // out of the 128 registers a 1024-lane workgroup has.  The empty statement makes the next counter wait for this result.
-#if defined(__HIP_DEVICE_COMPILE__)
-      asm volatile("" : "+v"(p0) : "v"((u32)lo[0]));
-#endif
-    }
-  }
-}
-
-// the polynomial c at the nodes 1..n into rows of `out`: F::muladd_small_lazy steps, one F::canon at the end
-template <class F, int D>
-__device__ __forceinline__ void eval_rows(const typename F::Ctx& ctx, const typename F::E (&c)[D + 1], u64* out, size_t stride, int n) {
-#pragma unroll 1
-  for (int i = 0; i < n; ++i) {
-    const u32 x = (u32)(i + 1);
-    typename F::E y = c[D];
-#pragma unroll
-    for (int k = D; k >= 1; --k) y = F::muladd_small_lazy(ctx, y, x, c[k - 1]);  // congruent, not yet canonical
-    Pack<F, 1> r;
-    r.v[0] = F::canon(y);
-    store_pack<F, 1, true>(out + (size_t)i * stride * F::LIMBS, r);
-  }
-}
-
 // Fused: double sharing s at blocks counter0 + s*B, B = BPE + Bs(T) + Bs(2T).  One kernel per threshold T, so that the
 // coefficients stay in registers and Horner has no tests in it.  Fields with F::muladd_small_lazy on 16-bit nodes (the Mersenne
 // fields, GF(2^128)).
@@ -185,12 +117,12 @@ __global__ __launch_bounds__(BLOCK) void k_hm_apply(typename F::Ctx ctx, u64* ou
   const size_t k0 = (g0 + blockIdx.z) * R;
   out += ((size_t)blockIdx.y * out_bstride + k0 * out_stride) * F::LIMBS;
   in += (size_t)blockIdx.y * in_bstride * F::LIMBS;
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
+  const size_t items = pack_items<VEC>(N);  // (the loop is the block's, not the lane's: every lane stages the tiles)
   const bool one_tile = n <= APPLY_NC;
   bool staged = false;
   for (size_t base = (size_t)blockIdx.x * BLOCK; base < items; base += (size_t)gridDim.x * BLOCK) {
     const size_t q = base + threadIdx.x;
-    const bool active = q < items, pair = VEC == 2 && q < npacks;
+    const bool active = q < items, pair = VEC == 2 && q < N / VEC;
     const size_t col = (VEC == 1 || pair) ? q * VEC : N - 1;  // the odd element after the last pair
     typename F::KAcc acc[R][VEC];
 #pragma unroll
@@ -299,11 +231,7 @@ __global__ __launch_bounds__(BLOCK) void k_hm_apply_thin(typename F::Ctx ctx, u6
   __syncthreads();
   out += (size_t)blockIdx.y * out_bstride * F::LIMBS;
   in += (size_t)blockIdx.y * in_bstride * F::LIMBS;
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) thin_at<F, VEC, KMAX>(ctx, out, out_stride, in, in_stride, Ms, m, n, q * VEC);
-    else thin_at<F, 1, KMAX>(ctx, out, out_stride, in, in_stride, Ms, m, n, N - 1);  // the odd element after the last pair
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) { thin_at<F, w, KMAX>(ctx, out, out_stride, in, in_stride, Ms, m, n, i); });
 }
 
 // ---- mask and finish -------------------------------------------------------------------------------------------------------
@@ -327,35 +255,15 @@ __global__ __launch_bounds__(BLOCK) void k_hm_mask(typename F::Ctx ctx, u64* d, 
   x += in_row;
   y += in_row;
   r2 += in_row;
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) mask_at<F, VEC>(ctx, d, x, y, r2, q * VEC);
-    else mask_at<F, 1>(ctx, d, x, y, r2, N - 1);
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) { mask_at<F, w>(ctx, d, x, y, r2, i); });
 }
-
-template <class F>
-struct Lambda {  // kernel-argument table (2 KiB for the 32-byte fields)
-  typename F::E v[FINISH_M_MAX];
-};
 
 // z[r][i .. i + W) for every row r: the opened value once, each row's r read and its z written where it lies
 template <class F, int W>
 __device__ __forceinline__ void finish_at(const typename F::Ctx& ctx, u64* z, size_t z_stride, const u64* dsh, size_t d_stride,
                                           const typename F::E* lam, int m, const u64* rr, size_t r_stride, size_t rows, size_t i) {
-  typename F::Acc acc[W];
-#pragma unroll
-  for (int v = 0; v < W; ++v) acc[v] = F::acc_zero();
-#pragma unroll 1
-  for (int j = 0; j < m; ++j) {  // m <= 64 <= every field's F::ACC_TERMS: no fold on the way
-    const Pack<F, W> dv = load_pack<F, W, true>(dsh + ((size_t)j * d_stride + i) * F::LIMBS);
-    const typename F::E l = lam[j];
-#pragma unroll
-    for (int v = 0; v < W; ++v) F::mac(ctx, acc[v], l, dv.v[v]);
-  }
   typename F::E opened[W];
-#pragma unroll
-  for (int v = 0; v < W; ++v) opened[v] = F::acc_fold(ctx, acc[v]);
+  open_at<F, W>(ctx, dsh, d_stride, lam, m, i, opened);
 #pragma unroll 1
   for (size_t r = 0; r < rows; ++r) {
     const Pack<F, W> rv = load_pack<F, W, true>(rr + (r * r_stride + i) * F::LIMBS);
@@ -368,15 +276,11 @@ __device__ __forceinline__ void finish_at(const typename F::Ctx& ctx, u64* z, si
 
 template <class F, int VEC>
 __global__ __launch_bounds__(BLOCK) void k_hm_finish(typename F::Ctx ctx, u64* z, size_t z_stride, const u64* dsh, size_t d_stride,
-                                                     Lambda<F> tab, int m, const u64* rr, size_t r_stride, size_t rows, size_t N) {
-  __shared__ typename F::E lam[FINISH_M_MAX];
+                                                     OpenTable<F> tab, int m, const u64* rr, size_t r_stride, size_t rows, size_t N) {
+  __shared__ typename F::E lam[OPEN_M_MAX];
   for (int j = threadIdx.x; j < m; j += BLOCK) lam[j] = tab.v[j];
   __syncthreads();
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) finish_at<F, VEC>(ctx, z, z_stride, dsh, d_stride, lam, m, rr, r_stride, rows, q * VEC);
-    else finish_at<F, 1>(ctx, z, z_stride, dsh, d_stride, lam, m, rr, r_stride, rows, N - 1);
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) { finish_at<F, w>(ctx, z, z_stride, dsh, d_stride, lam, m, rr, r_stride, rows, i); });
 }
 
 }  // namespace
@@ -389,18 +293,12 @@ __global__ __launch_bounds__(BLOCK) void k_hm_finish(typename F::Ctx ctx, u64* z
 namespace {
 
 constexpr size_t FUSED_TMAX = 3;        // the fused kernel keeps 2t + 1 <= 7 coefficients in registers
-constexpr size_t PARTY_MAX = 65535;     // the node i + 1 as a small integer (GF(2^128): F::muladd_small takes 16 bits)
-// The largest degree the two-pass path takes: beyond it scl_hip_shamir_share evaluates chunk by chunk, staging each chunk's
-// power table from host memory and synchronising the stream before it returns -- a call of this library never synchronises
-constexpr size_t DEG_MAX_NARROW = 48;   // 8- and 16-byte elements
-constexpr size_t DEG_MAX_WIDE = 16;     // 32-byte elements
 
 bool fused_double(int field, size_t t, unsigned flags) {
   return !(flags & SCL_HM_TWO_PASS) && t <= FUSED_TMAX && (field == SCL_M61 || field == SCL_M127 || field == SCL_GF2_128);
 }
 size_t deg_blocks(size_t limbs, size_t d) { return ((d + 1) * 8 * limbs + 15) / 16; }
 size_t double_blocks(size_t limbs, size_t t) { return bpe_of(limbs) + deg_blocks(limbs, t) + deg_blocks(limbs, 2 * t); }
-size_t deg_max(size_t limbs) { return limbs == 4 ? DEG_MAX_WIDE : DEG_MAX_NARROW; }
 bool double_nt_ok(size_t limbs, size_t n, size_t t) { return n <= PARTY_MAX && t <= deg_max(limbs) / 2 && n > 2 * t; }
 
 constexpr size_t EXTENT_MAX = (size_t)1 << 60;  // elements a matrix may span: no extent below wraps
@@ -444,9 +342,7 @@ int scl_hm_double_share_prg(int field, uint64_t* lo_dev, uint64_t* hi_dev, size_
   const Span sl = span_of(lo_dev, n, stride, N, L), sh = span_of(hi_dev, n, stride, N, L);
   if (overlap(sl, sh)) return fail(SCL_ERR_BAD_ARG, "double_share_prg: the share matrices overlap");
   const uint64_t B = double_blocks(L, t);
-  // N * B blocks from counter0 (and the slack aes_key_range adds) must not wrap the 64-bit counter
-  const uint64_t room = ~(uint64_t)0 - 128;
-  if (counter0 > room || N > (room - counter0) / B) return fail(SCL_ERR_BAD_ARG, "double_share_prg: the block range wraps the 64-bit counter");
+  if (const int rc = check_counter_range("double_share_prg", counter0, N, B)) return rc;
   const bool fused = fused_double(field, t, flags);
   if (!fused) {
     const size_t need = scl_hm_double_scratch_bytes(field, N, n, t, flags);
@@ -522,36 +418,22 @@ int scl_hm_apply(int field, uint64_t* out_dev, size_t out_stride, size_t out_bat
       uint64_t* o = out_dev + b0 * out_batch_stride * L;
       const uint64_t* in = in_dev + b0 * in_batch_stride * L;
       if (thin) {
-#define THIN_LAUNCH(VV, KK)                                                                                                            \
-  hipLaunchKernelGGL((k_hm_apply_thin<F, VV, KK>), dim3(grid_for(VV == 2 ? N / 2 + (N & 1) : N), (unsigned)nb), dim3(BLOCK), 0, S(stream), ctx, \
-                     o, out_stride, out_batch_stride, in, in_stride, in_batch_stride, M_dev, ldm, (int)m, (int)n, N)
-#define THIN_CASE(KK)                                  \
-  case KK:                                             \
-    if constexpr (F::LIMBS == 1) {                     \
-      if (two) THIN_LAUNCH(2, KK);                     \
-      else THIN_LAUNCH(1, KK);                         \
-    } else {                                           \
-      THIN_LAUNCH(1, KK);                              \
-    }                                                  \
+#define THIN_CASE(KK)                                                                                                              \
+  case KK:                                                                                                                         \
+    PACK_LAUNCH((k_hm_apply_thin, F, KK), two, dim3(grid_for_packs(two, N), (unsigned)nb), S(stream), ctx, o, out_stride, out_batch_stride, in, \
+                in_stride, in_batch_stride, M_dev, ldm, (int)m, (int)n, N);                                                         \
     break;
         switch ((n + 3) / 4 * 4) {
           THIN_CASE(4) THIN_CASE(8) THIN_CASE(12) THIN_CASE(16)
           default: return fail(SCL_ERR_BAD_ARG, "apply: internal width");
         }
 #undef THIN_CASE
-#undef THIN_LAUNCH
-        HIP_TRY(hipGetLastError());
         continue;
       }
       for (size_t g0 = 0; g0 < groups; g0 += GRID_Y_MAX) {
         const size_t ng = groups - g0 < GRID_Y_MAX ? groups - g0 : GRID_Y_MAX;
-        if (two)
-          hipLaunchKernelGGL((k_hm_apply<F, F::LIMBS == 1 ? 2 : 1, R>), dim3(grid_for(N / 2 + (N & 1)), (unsigned)nb, (unsigned)ng), dim3(BLOCK),
-                             0, S(stream), ctx, o, out_stride, out_batch_stride, in, in_stride, in_batch_stride, M_dev, ldm, g0, m, (int)n, N);
-        else
-          hipLaunchKernelGGL((k_hm_apply<F, 1, R>), dim3(grid_for(N), (unsigned)nb, (unsigned)ng), dim3(BLOCK), 0, S(stream), ctx, o,
-                             out_stride, out_batch_stride, in, in_stride, in_batch_stride, M_dev, ldm, g0, m, (int)n, N);
-        HIP_TRY(hipGetLastError());
+        PACK_LAUNCH((k_hm_apply, F, R), two, dim3(grid_for_packs(two, N), (unsigned)nb, (unsigned)ng), S(stream), ctx, o, out_stride,
+                    out_batch_stride, in, in_stride, in_batch_stride, M_dev, ldm, g0, m, (int)n, N);
       }
     }
     return SCL_OK;
@@ -583,13 +465,8 @@ int scl_hm_mul_mask(int field, uint64_t* d_dev, size_t d_stride, const uint64_t*
       const size_t r = rows - r0 < GRID_Y_MAX ? rows - r0 : GRID_Y_MAX;
       uint64_t* o = d_dev + r0 * d_stride * L;
       const size_t in0 = r0 * op_stride * L;
-      if (two)
-        hipLaunchKernelGGL((k_hm_mask<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1)), (unsigned)r), dim3(BLOCK), 0, S(stream), ctx,
-                           o, d_stride, x_dev + in0, y_dev + in0, r2_dev + in0, op_stride, N);
-      else
-        hipLaunchKernelGGL((k_hm_mask<F, 1>), dim3(grid_for(N), (unsigned)r), dim3(BLOCK), 0, S(stream), ctx, o, d_stride, x_dev + in0,
-                           y_dev + in0, r2_dev + in0, op_stride, N);
-      HIP_TRY(hipGetLastError());
+      PACK_LAUNCH((k_hm_mask, F), two, dim3(grid_for_packs(two, N), (unsigned)r), S(stream), ctx, o, d_stride, x_dev + in0, y_dev + in0,
+                  r2_dev + in0, op_stride, N);
     }
     return SCL_OK;
   });
@@ -602,7 +479,7 @@ int scl_hm_mul_finish(int field, uint64_t* z_dev, size_t z_stride, const uint64_
   Mont128::Ctx mont = {};
   if (const int rc = mont_latch(field, mont)) return rc;
   const size_t L = limbs_of(field);
-  if (m == 0 || m > (size_t)FINISH_M_MAX)
+  if (m == 0 || m > (size_t)OPEN_M_MAX)
     return fail(SCL_ERR_BAD_ARG, "mul_finish: m must be in 1..64 (lambda travels with the launch); beyond that open with scl_hip_shamir_recover "
                                  "and subtract with scl_hip_ew");
   if (!z_dev || !dsh_dev || !lambda_host || !r_dev) return fail(SCL_ERR_BAD_ARG, "mul_finish: NULL operand");
@@ -619,15 +496,9 @@ int scl_hm_mul_finish(int field, uint64_t* z_dev, size_t z_stride, const uint64_
   return with_field(field, mont, [&](auto f, auto ctx) -> int {
     using F = decltype(f);
     if (const int rc = need_device()) return rc;
-    Lambda<F> tab;
-    for (size_t j = 0; j < (size_t)FINISH_M_MAX; ++j) tab.v[j] = j < m ? F::ld(lambda_host + j * F::LIMBS) : F::zero();
-    if (two_per_lane(L, {z_dev, dsh_dev, r_dev}, {rows > 1 ? z_stride : 0, rows > 1 ? r_stride : 0, m > 1 ? d_stride : 0}))
-      hipLaunchKernelGGL((k_hm_finish<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1))), dim3(BLOCK), 0, S(stream), ctx, z_dev,
-                         z_stride, dsh_dev, d_stride, tab, (int)m, r_dev, r_stride, rows, N);
-    else
-      hipLaunchKernelGGL((k_hm_finish<F, 1>), dim3(grid_for(N)), dim3(BLOCK), 0, S(stream), ctx, z_dev, z_stride, dsh_dev, d_stride, tab,
-                         (int)m, r_dev, r_stride, rows, N);
-    HIP_TRY(hipGetLastError());
+    const bool two = two_per_lane(L, {z_dev, dsh_dev, r_dev}, {rows > 1 ? z_stride : 0, rows > 1 ? r_stride : 0, m > 1 ? d_stride : 0});
+    PACK_LAUNCH((k_hm_finish, F), two, dim3(grid_for_packs(two, N)), S(stream), ctx, z_dev, z_stride, dsh_dev, d_stride,
+                make_open_table<F>(lambda_host, m), (int)m, r_dev, r_stride, rows, N);
     return SCL_OK;
   });
 }

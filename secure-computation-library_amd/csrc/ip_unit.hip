@@ -9,7 +9,7 @@
 //   k_ip_matmul   one lane = one column of batch blockIdx.y and the TI x TL output tile blockIdx.z: TI TL accumulators, TI + TL
 //                 operand loads per k, rows and columns past the matrix edge clamped and discarded as k_matmul clamps; one term
 //                 count for all accumulators, which fold together
-// A 1 x 1 product is the dot kernel (rows = batches).  The streaming kernel keeps the conventions of csrc/hm_unit.hip: 256-lane
+// A 1 x 1 product is the dot kernel (rows = batches).  The streaming kernel keeps the conventions of csrc/unit_device.hpp: 256-lane
 // blocks, 16-byte non-temporal accesses, the pack width of Mersenne61 chosen on the host per call, the odd last element taken by
 // the lane after the last pair.  The matrix kernel reads its operands cached: every element is read once per tile row or column.
 // The engine is reached through the prototypes of scl_hip.h only.
@@ -18,11 +18,10 @@
 #include "../../include/scl_hip_ip.h"
 #include "../../include/scl_hip/detail/ip.hpp"
 #include "kernels.hpp"
+#include "unit_device.hpp"
 
 namespace sclhip {
 namespace {
-
-constexpr size_t GRID_YZ_MAX = 65535;
 
 // terms whose 2 W loads a lane issues before it consumes the first product: 16 bytes each for one- and two-limb fields (8 loads
 // in flight), 32 bytes for the wide ones (4 loads of two requests each) -- docs/kernels/ip.md
@@ -85,11 +84,7 @@ __global__ __launch_bounds__(BLOCK) void k_ip_dot(typename F::Ctx ctx, u64* d, s
   x += (size_t)blockIdx.y * x_rs * F::LIMBS;
   y += (size_t)blockIdx.y * y_rs * F::LIMBS;
   if (r2) r2 += (size_t)blockIdx.y * r2_rs * F::LIMBS;
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) dot_at<F, VEC>(ctx, d, x, x_ts, y, y_ts, r2, nterms, q * VEC);
-    else dot_at<F, 1>(ctx, d, x, x_ts, y, y_ts, r2, nterms, N - 1);  // the odd element after the last pair
-  }
+  for_each_pack<VEC>(N, [&](auto w, size_t i) { dot_at<F, w>(ctx, d, x, x_ts, y, y_ts, r2, nterms, i); });
 }
 
 // the output tile a lane owns: what the registers hold without scratch (docs/kernels/ip.md has the figures)
@@ -168,19 +163,6 @@ namespace {
 
 constexpr size_t DIM_MAX = 65535;  // a, K and b of a matrix product
 
-// An operand addressed with several strides, as span.hpp sees it: ONE row of its bounding extent
-// sum_j (count_j - 1) stride_j + N elements.  false: the extent does not fit size_t.
-bool extent_of(std::initializer_list<std::pair<size_t, size_t>> dims, size_t N, size_t* out) {
-  size_t e = N;
-  for (const auto& d : dims) {
-    size_t part = 0;
-    if (d.first == 0) continue;
-    if (__builtin_mul_overflow(d.first - 1, d.second, &part) || __builtin_add_overflow(e, part, &e)) return false;
-  }
-  *out = e;
-  return true;
-}
-
 // d against the inputs (alias::conflict names the pair), then d against r2, which it may be exactly (`same`)
 int alias_check(const char* who, size_t esz, const void* d, size_t de, const void* x, size_t xe, const void* y, size_t ye, const void* r2, size_t re,
                 bool same) {
@@ -198,17 +180,12 @@ template <class F>
 int launch_dot(const typename F::Ctx& ctx, bool two, uint64_t* d, size_t d_rs, const uint64_t* x, size_t x_ts, size_t x_rs, const uint64_t* y,
                size_t y_ts, size_t y_rs, const uint64_t* r2, size_t r2_rs, size_t terms, size_t rows, size_t N, void* stream) {
   constexpr size_t L = F::LIMBS;
-  for (size_t r0 = 0; r0 < rows; r0 += GRID_YZ_MAX) {
-    const size_t r = rows - r0 < GRID_YZ_MAX ? rows - r0 : GRID_YZ_MAX;
+  for (size_t r0 = 0; r0 < rows; r0 += GRID_Y_MAX) {
+    const size_t r = rows - r0 < GRID_Y_MAX ? rows - r0 : GRID_Y_MAX;
     uint64_t* o = d + r0 * d_rs * L;
     const uint64_t *xx = x + r0 * x_rs * L, *yy = y + r0 * y_rs * L, *rr = r2 ? r2 + r0 * r2_rs * L : nullptr;
-    if (two)
-      hipLaunchKernelGGL((k_ip_dot<F, F::LIMBS == 1 ? 2 : 1>), dim3(grid_for(N / 2 + (N & 1)), (unsigned)r), dim3(BLOCK), 0, S(stream), ctx, o, d_rs,
-                         xx, x_ts, x_rs, yy, y_ts, y_rs, rr, r2_rs, terms, N);
-    else
-      hipLaunchKernelGGL((k_ip_dot<F, 1>), dim3(grid_for(N), (unsigned)r), dim3(BLOCK), 0, S(stream), ctx, o, d_rs, xx, x_ts, x_rs, yy, y_ts, y_rs,
-                         rr, r2_rs, terms, N);
-    HIP_TRY(hipGetLastError());
+    PACK_LAUNCH((k_ip_dot, F), two, dim3(grid_for_packs(two, N), (unsigned)r), S(stream), ctx, o, d_rs, xx, x_ts, x_rs, yy, y_ts, y_rs, rr, r2_rs,
+                terms, N);
   }
   return SCL_OK;
 }
@@ -299,10 +276,10 @@ int scl_ip_matmul_mask(int field, uint64_t* d_dev, size_t d_stride, size_t d_bat
     }
     constexpr int TI = Tile<F>::TI, TL = Tile<F>::TL;
     const size_t tiles_i = (a + TI - 1) / TI, tiles_l = (b + TL - 1) / TL, tiles = tiles_i * tiles_l;
-    for (size_t q0 = 0; q0 < batch; q0 += GRID_YZ_MAX) {
-      const size_t nq = batch - q0 < GRID_YZ_MAX ? batch - q0 : GRID_YZ_MAX;
-      for (size_t t0 = 0; t0 < tiles; t0 += GRID_YZ_MAX) {
-        const size_t nt = tiles - t0 < GRID_YZ_MAX ? tiles - t0 : GRID_YZ_MAX;
+    for (size_t q0 = 0; q0 < batch; q0 += GRID_Y_MAX) {
+      const size_t nq = batch - q0 < GRID_Y_MAX ? batch - q0 : GRID_Y_MAX;
+      for (size_t t0 = 0; t0 < tiles; t0 += GRID_Y_MAX) {
+        const size_t nt = tiles - t0 < GRID_Y_MAX ? tiles - t0 : GRID_Y_MAX;
         hipLaunchKernelGGL((k_ip_matmul<F, TI, TL>), dim3(grid_for(N), (unsigned)nq, (unsigned)nt), dim3(BLOCK), 0, S(stream), ctx,
                            d_dev + q0 * d_batch_stride * L, d_stride, d_batch_stride, x_dev + q0 * x_batch_stride * L, x_stride, x_batch_stride,
                            y_dev + q0 * y_batch_stride * L, y_stride, y_batch_stride, r2_dev ? r2_dev + q0 * r2_batch_stride * L : nullptr, r2_stride,

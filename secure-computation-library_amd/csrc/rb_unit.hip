@@ -10,13 +10,14 @@
 //                      flight during it; elsewhere a row is loaded when it is used
 // No LDS, no atomics, no allocation, no synchronisation: a lane's chain is 70 to about 385 dependent products, independent work
 // comes from the other waves of the SIMD.  256-lane blocks, 16-byte non-temporal accesses, the odd last element of a Mersenne61
-// row taken by the lane after the last pair (the conventions of csrc/hm_unit.hip).  The engine is reached through the
+// row taken by the lane after the last pair (the conventions of csrc/unit_device.hpp).  The engine is reached through the
 // prototypes of scl_hip.h only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/scl_hip_rb.h"
 #include "../../include/scl_hip/detail/rb.hpp"
 #include "kernels.hpp"
+#include "unit_device.hpp"
 
 namespace sclhip {
 namespace {
@@ -77,10 +78,16 @@ __device__ __forceinline__ void bits_at(const typename F::Ctx& ctx, const RbPara
 template <class F, int VEC, bool PRE>
 __global__ __launch_bounds__(BLOCK) void k_rb_bits_finish(typename F::Ctx ctx, RbParams<F> prm, u64* b, size_t b_stride, unsigned char* status,
                                                           const u64* u, const u64* r, size_t r_stride, size_t rows, size_t N) {
-  const size_t npacks = N / VEC, items = npacks + (VEC == 2 ? (N & 1) : 0);
-  for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
-    if (VEC == 1 || q < npacks) bits_at<F, VEC, PRE>(ctx, prm, b, b_stride, status, u, r, r_stride, rows, q * VEC);
-    else bits_at<F, 1, PRE>(ctx, prm, b, b_stride, status, u, r, r_stride, rows, N - 1);  // the odd element after the last pair
+  if constexpr (PRE) {
+    // the preloading form keeps the loop spelled out: through for_each_pack's callable the compiler schedules the sixteen row
+    // loads and the chain differently (some instructions more for one column per lane, some fewer for two)
+    const size_t pairs = N / VEC, items = pack_items<VEC>(N);
+    for (size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x; q < items; q += (size_t)gridDim.x * BLOCK) {
+      if (VEC == 1 || q < pairs) bits_at<F, VEC, true>(ctx, prm, b, b_stride, status, u, r, r_stride, rows, q * VEC);
+      else bits_at<F, 1, true>(ctx, prm, b, b_stride, status, u, r, r_stride, rows, N - 1);  // the odd element after the last pair
+    }
+  } else {
+    for_each_pack<VEC>(N, [&](auto w, size_t i) { bits_at<F, w, false>(ctx, prm, b, b_stride, status, u, r, r_stride, rows, i); });
   }
 }
 
@@ -112,17 +119,8 @@ RbParams<F> params_for(const typename F::Ctx& ctx) {
 
 // the tags this library refuses, each with its reason; SCL_OK for the five prime fields
 int check_tag(const std::string& w, int field) {
-  if (field == SCL_GF2_128)
-    return fail(SCL_ERR_BAD_ARG, w + ": SCL_GF2_128 is refused: squaring is a bijection of GF(2^128), every element has one root and r / sqrt(r^2) is always 1");
-  if (is_ring(field)) return fail(SCL_ERR_BAD_ARG, w + ": a ring tag is refused: a ring Z2k is not a field, square roots and Shamir sharings need one");
-  if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, w + ": unknown field tag");
-  return SCL_OK;
-}
-
-int check_ptr(const std::string& w, size_t L, const char* name, const void* p) {
-  if (!p) return fail(SCL_ERR_BAD_ARG, w + ": " + name + " is NULL");
-  if (reinterpret_cast<uintptr_t>(p) & (L == 1 ? 7 : 15)) return fail(SCL_ERR_BAD_ARG, w + ": " + name + (L == 1 ? " not 8-byte aligned" : " not 16-byte aligned"));
-  return SCL_OK;
+  return check_prime_field(w, field, "squaring is a bijection of GF(2^128), every element has one root and r / sqrt(r^2) is always 1",
+                           "a ring Z2k is not a field, square roots and Shamir sharings need one");
 }
 
 }  // namespace
@@ -184,24 +182,15 @@ int scl_rb_bits_finish(int field, uint64_t* b_dev, size_t b_stride, unsigned cha
     } else {
       if (const int rc = need_device()) return rc;
       const RbParams<F> prm = params_for<F>(ctx);
-      if constexpr (F::LIMBS == 1) {
-        const bool two = two_per_lane(L, {b_dev, u_dev, r_dev}, {rows > 1 ? b_stride : 0, rows > 1 ? r_stride : 0});
-        const dim3 grid(grid_for(two ? N / 2 + (N & 1) : N));
-#define RB_FINISH(VV, PP) \
-  hipLaunchKernelGGL((k_rb_bits_finish<F, VV, PP>), grid, dim3(BLOCK), 0, S(stream), ctx, prm, b_dev, b_stride, status_dev, u_dev, r_dev, r_stride, rows, N)
+      const bool two = two_per_lane(L, {b_dev, u_dev, r_dev}, {rows > 1 ? b_stride : 0, rows > 1 ? r_stride : 0});
+      const dim3 grid(grid_for_packs(two, N));
+      if constexpr (F::LIMBS == 1) {  // (the preloading form exists for the one-limb field only)
         if (rows <= (size_t)RB_PRELOAD_ROWS) {
-          if (two) RB_FINISH(2, true);
-          else RB_FINISH(1, true);
-        } else {
-          if (two) RB_FINISH(2, false);
-          else RB_FINISH(1, false);
+          PACK_LAUNCH((k_rb_bits_finish, F, true), two, grid, S(stream), ctx, prm, b_dev, b_stride, status_dev, u_dev, r_dev, r_stride, rows, N);
+          return SCL_OK;
         }
-#undef RB_FINISH
-      } else {
-        hipLaunchKernelGGL((k_rb_bits_finish<F, 1, false>), dim3(grid_for(N)), dim3(BLOCK), 0, S(stream), ctx, prm, b_dev, b_stride, status_dev, u_dev,
-                           r_dev, r_stride, rows, N);
       }
-      HIP_TRY(hipGetLastError());
+      PACK_LAUNCH((k_rb_bits_finish, F, false), two, grid, S(stream), ctx, prm, b_dev, b_stride, status_dev, u_dev, r_dev, r_stride, rows, N);
       return SCL_OK;
     }
   });

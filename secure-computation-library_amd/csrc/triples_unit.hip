@@ -5,8 +5,9 @@
 // c = a b, all drawn from one util::PRG before the next triple begins.  Every PRG-driven entry point of the engine puts secret
 // s at counter0 + s * (its own block count), so no composition of them reaches that order; the AES blocks are counter-addressed,
 // though, so a lane that deals triple s encrypts the blocks [counter0 + s B, counter0 + (s+1) B) itself (the header states B
-// and the order of the draws).  Three kernels, all on the four-table AES of kernels.hpp (1024-lane workgroups, the 128 KiB of
-// tables at the bottom of 132 KiB of dynamic LDS, one workgroup per CU behind a grid-stride loop):
+// and the order of the draws; the draws themselves are csrc/prg_deal.hpp, which hm_unit.hip shares).  Three kernels, all on
+// the four-table AES of kernels.hpp (1024-lane workgroups, the 128 KiB of tables at the bottom of 132 KiB of dynamic LDS, one
+// workgroup per CU behind a grid-stride loop):
 //   k_triples_additive_prg  one lane = one triple (Mersenne61 on 16-byte bases and an even stride: two): B blocks, one product,
 //                           3 n row elements from three running differences
 //   k_triples_shamir_prg    one lane = one triple, the three polynomials one after another (at most t + 1 coefficients live),
@@ -19,25 +20,10 @@
 
 #include "../../include/scl_hip_prep.h"
 #include "kernels.hpp"
+#include "prg_deal.hpp"
 
 namespace sclhip {
 namespace {
-
-template <class F>
-constexpr int bpe() {  // FF::random burns ceil(byteSize/16) blocks (ff.h:72-76)
-  return F::LIMBS >= 2 ? F::LIMBS / 2 : 1;
-}
-
-// one FF::random at block c0: a one-limb element is the first 8 bytes of its block
-template <class F>
-__device__ __forceinline__ typename F::E draw_elem(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64 c0) {
-  constexpr int BPE = bpe<F>();
-  u64 lo[BPE], hi[BPE];
-#pragma unroll
-  for (int b = 0; b < BPE; ++b) aes.block(key, c0 + b, lo[b], hi[b]);
-  if constexpr (F::LIMBS == 1) return F::from_le_word(ctx, lo[0]);
-  else return elem_from_blocks<F>(ctx, lo, hi);
-}
 
 // additive: triple s = q*VEC + v at blocks counter0 + s*B, B = (2 + 3(n-1)) BPE; matrix m (0 a, 1 b, 2 c) draws its n-1 random
 // shares at element index 2 + m(n-1) + i of the triple, the last row is the secret minus their sum
@@ -75,48 +61,12 @@ __global__ __launch_bounds__(ABLOCK) void k_triples_additive_prg(typename F::Ctx
   }
 }
 
-// Blocks of one Vector::random(t+1) draw
-template <class F>
-__host__ __device__ inline u64 poly_blocks(u64 t) {
-  return ((t + 1) * (u64)(8 * F::LIMBS) + 15) / 16;
-}
-
-// coefficients 1..T of the polynomial whose Vector::random(T+1) draw starts at block p0 (element 0 is discarded, shamir.h:57):
-// one-limb fields hold elements 2j and 2j+1 in block j, wider ones element k in blocks k*BPE ..
-template <class F, int T>
-__device__ __forceinline__ void draw_poly(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64 p0,  // (by value)
-                                          typename F::E (&c)[T + 1]) {
-  if constexpr (F::LIMBS == 1) {
-#pragma unroll
-    for (int j = 0; 2 * j <= T; ++j) {
-      u64 lo, hi;
-      aes.block(key, p0 + j, lo, hi);
-      if (j > 0) c[2 * j] = F::from_le_word(ctx, lo);
-      if (2 * j + 1 <= T) c[2 * j + 1] = F::from_le_word(ctx, hi);
-    }
-  } else {
-    constexpr int BPE = bpe<F>();
-#pragma unroll
-    for (int k = 1; k <= T; ++k) {
-      u64 lo[BPE], hi[BPE];
-#pragma unroll
-      for (int b = 0; b < BPE; ++b) aes.block(key, p0 + (u64)k * BPE + b, lo[b], hi[b]);
-      c[k] = elem_from_blocks<F>(ctx, lo, hi);
-      // one coefficient's blocks at a time: left alone the compiler runs all T draws abreast (some ten registers each) and
-      // runs out of the 128 a 1024-lane workgroup has.  The empty statement makes the next counter wait for this result.
-#if defined(__HIP_DEVICE_COMPILE__)
-      asm volatile("" : "+v"(p0) : "v"((u32)lo[0]));
-#endif
-    }
-  }
-}
-
 // every triple of the launch at threshold T: the three polynomials one after another, the parties in a rolled loop
 template <class F, int T>
 __device__ __forceinline__ void deal_shamir(const typename F::Ctx& ctx, const Aes4& aes, const AesKey& key, u64* a_out, u64* b_out,
                                             u64* c_out, size_t stride, u64 counter0, int n, size_t N) {
   constexpr int BPE = bpe<F>();
-  constexpr u64 Bs = ((u64)(T + 1) * 8 * F::LIMBS + 15) / 16, B = 2 * BPE + 3 * Bs;
+  constexpr u64 Bs = poly_blocks<F>(T), B = 2 * BPE + 3 * Bs;
   SCL_AES4_GRID_STRIDE(s, N) {
     const u64 c0 = counter0 + s * B;
     const typename F::E a = draw_elem<F>(ctx, aes, key, c0), b = draw_elem<F>(ctx, aes, key, c0 + BPE);
@@ -126,18 +76,7 @@ __device__ __forceinline__ void deal_shamir(const typename F::Ctx& ctx, const Ae
       typename F::E c[T + 1];
       c[0] = m == 0 ? a : m == 1 ? b : ab;
       draw_poly<F, T>(ctx, aes, key, c0 + 2 * BPE + (u64)m * Bs, c);
-      u64* out = (m == 0 ? a_out : m == 1 ? b_out : c_out) + s * F::LIMBS;
-#pragma unroll 1
-      for (int i = 0; i < n; ++i) {
-        const u32 x = (u32)(i + 1);
-        typename F::E y = c[T];
-#pragma unroll
-        for (int k = T; k >= 1; --k) y = F::muladd_small_lazy(ctx, y, x, c[k - 1]);  // congruent, not yet canonical
-        y = F::canon(y);
-        Pack<F, 1> r;
-        r.v[0] = y;
-        store_pack<F, 1, true>(out + (size_t)i * stride * F::LIMBS, r);
-      }
+      eval_rows<F, T>(ctx, c, (m == 0 ? a_out : m == 1 ? b_out : c_out) + s * F::LIMBS, stride, n);
     }
   }
 }
@@ -201,11 +140,6 @@ __global__ __launch_bounds__(ABLOCK) void k_triple_coeff_rows(typename F::Ctx ct
 namespace {
 
 constexpr size_t FUSED_TMAX = 7;        // the fused Shamir kernel keeps t + 1 <= 8 coefficients in registers
-constexpr size_t PARTY_MAX = 65535;     // Shamir: the node i + 1 as a small integer (GF(2^128): F::muladd_small takes 16 bits)
-// The largest threshold the two-pass path takes: beyond it scl_hip_shamir_share evaluates chunk by chunk, staging each chunk's
-// power table from host memory and synchronising the stream before it returns -- a call of this library never synchronises
-constexpr size_t T_MAX_NARROW = 48;     // 8- and 16-byte elements
-constexpr size_t T_MAX_WIDE = 16;       // 32-byte elements
 
 bool fused_shamir(int field, size_t t, unsigned flags) {
   return !(flags & SCL_PREP_TWO_PASS) && t <= FUSED_TMAX && (field == SCL_M61 || field == SCL_M127 || field == SCL_GF2_128);
@@ -214,8 +148,7 @@ bool fused_shamir(int field, size_t t, unsigned flags) {
 size_t additive_blocks(size_t limbs, size_t n) { return (2 + 3 * (n - 1)) * bpe_of(limbs); }
 size_t shamir_blocks(size_t limbs, size_t t) { return 2 * bpe_of(limbs) + 3 * (((t + 1) * 8 * limbs + 15) / 16); }
 bool additive_n_ok(size_t n) { return n >= 2 && n <= 0x7fffffffu / 4; }
-size_t shamir_t_max(size_t limbs) { return limbs == 4 ? T_MAX_WIDE : T_MAX_NARROW; }
-bool shamir_nt_ok(size_t limbs, size_t n, size_t t) { return n >= 1 && n <= PARTY_MAX && t <= shamir_t_max(limbs); }
+bool shamir_nt_ok(size_t limbs, size_t n, size_t t) { return n >= 1 && n <= PARTY_MAX && t <= deg_max(limbs); }
 
 // what both deal calls check alike, in the order the header lists it; B = blocks per triple
 int check_matrices(const char* who, size_t limbs, uint64_t* a, uint64_t* b, uint64_t* c, size_t stride, size_t N, size_t n, uint64_t B,
@@ -227,10 +160,7 @@ int check_matrices(const char* who, size_t limbs, uint64_t* a, uint64_t* b, uint
   if (n > ((size_t)1 << 60) / stride / limbs) return fail(SCL_ERR_BAD_ARG, w + ": n * stride overflows");
   const Span sa = span_of(a, n, stride, N, limbs), sb = span_of(b, n, stride, N, limbs), sc = span_of(c, n, stride, N, limbs);
   if (overlap(sa, sb) || overlap(sa, sc) || overlap(sb, sc)) return fail(SCL_ERR_BAD_ARG, w + ": the share matrices overlap");
-  // N * B blocks from counter0 (and the slack aes_key_range adds) must not wrap the 64-bit counter
-  const uint64_t room = ~(uint64_t)0 - 128;
-  if (counter0 > room || N > (room - counter0) / B) return fail(SCL_ERR_BAD_ARG, w + ": the block range wraps the 64-bit counter");
-  return SCL_OK;
+  return check_counter_range(w, counter0, N, B);
 }
 
 }  // namespace
@@ -296,7 +226,7 @@ int scl_prep_triples_shamir_prg(int field, uint64_t* a_dev, uint64_t* b_dev, uin
   if (flags & ~SCL_PREP_TWO_PASS) return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: unknown flags bit (only bit 0, two-pass, is defined)");
   const size_t L = limbs_of(field);
   if (!shamir_nt_ok(L, n, t))
-    return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: n must be in 1..65535 and the threshold t at most " + std::to_string(shamir_t_max(L)) +
+    return fail(SCL_ERR_BAD_ARG, "triples_shamir_prg: n must be in 1..65535 and the threshold t at most " + std::to_string(deg_max(L)) +
                                      " for this field (beyond it the engine's share call synchronises the stream)");
   const uint64_t B = shamir_blocks(L, t);
   if (const int rc = check_matrices("triples_shamir_prg", L, a_dev, b_dev, c_dev, stride, N, n, B, counter0)) return rc;

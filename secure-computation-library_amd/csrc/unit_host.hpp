@@ -5,9 +5,15 @@
 //   SCL_UNIT_ENGINE   a unit of libscl_hip.so (capi.hip, ec_, ecdsa_, pedersen_, hash_unit.hip, merkle_leaves.hip): the
 //                     diagnostics go to the engine's slot, sclhip_state::g_err, which capi.hip defines; the generic part only.
 //                     Without it the unit is an extension library beside the engine (libscl_hip_mpc / _prep / _hm / _ip / _vf / _rb / _fx):
-//                     it owns its slot and, serving every field from one unit, takes the field part too, which wants
-//                     sclhip::BLOCK declared -- kernels.hpp's, or the unit's own (beaver_unit.hip).
-//   SCL_UNIT_AES      the unit launches four-table AES kernels: the AES part, which needs kernels.hpp.
+//                     it owns its slot and, serving every field from one unit, takes the field part too: the dispatch on the
+//                     field tag and the latch rule, the checks the entry points share (check_align, check_ptr,
+//                     check_prime_field, extent_of), and the host half of unit_device.hpp -- the launch rule of the pack
+//                     kernels (two_per_lane, grid_for_packs, PACK_LAUNCH, rows in chunks of GRID_Y_MAX) and make_open_table.
+//                     For BLOCK and OpenTable the field part includes unit_device.hpp itself, and with it kernels.hpp: every
+//                     extension unit has both whether it names them or not, and a unit includes them before its kernels only
+//                     because its kernels use them.
+//   SCL_UNIT_AES      the unit launches four-table AES kernels: the AES part -- the launch, and for the dealers of prg_deal.hpp
+//                     the limits on the parties and the degree and the check of the counter range.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -75,12 +81,15 @@ int alias_check(const char* who, std::initializer_list<sclhip::alias::Operand> o
 
 // ---- the field part --------------------------------------------------------------------------------------------------------
 #ifndef SCL_UNIT_ENGINE
+#include <utility>
+
 #include "../../include/scl_hip/detail/field.hpp"
+#include "unit_device.hpp"  // BLOCK, OpenTable
 
 namespace {
 using namespace sclhip;
 
-constexpr size_t GRID_Y_MAX = 65535;
+constexpr size_t GRID_Y_MAX = 65535;  // rows (and, with a third dimension, tiles or groups) one launch takes: the sites chunk by it
 
 unsigned grid_for(size_t items) {  // one pack per lane; past 2^31 - 1 blocks the kernels' grid-stride loops take over
   const size_t blocks = (items + BLOCK - 1) / BLOCK;
@@ -162,6 +171,35 @@ int check_align(const char* who, size_t limbs, std::initializer_list<const void*
   return SCL_OK;
 }
 
+// `w`: the entry point; `name`: the parameter the message names
+int check_ptr(const std::string& w, size_t L, const char* name, const void* p) {
+  if (!p) return fail(SCL_ERR_BAD_ARG, w + ": " + name + " is NULL");
+  if (reinterpret_cast<uintptr_t>(p) & (L == 1 ? 7 : 15)) return fail(SCL_ERR_BAD_ARG, w + ": " + name + (L == 1 ? " not 8-byte aligned" : " not 16-byte aligned"));
+  return SCL_OK;
+}
+
+// a library of the five prime fields: the tags it refuses, GF(2^128) and the rings each with the library's own reason
+int check_prime_field(const std::string& w, int field, const char* gf_reason, const char* ring_reason) {
+  if (field == SCL_GF2_128) return fail(SCL_ERR_BAD_ARG, w + ": SCL_GF2_128 is refused: " + gf_reason);
+  if (is_ring(field)) return fail(SCL_ERR_BAD_ARG, w + ": a ring tag is refused: " + ring_reason);
+  if (!is_field(field)) return fail(SCL_ERR_BAD_ARG, w + ": unknown field tag");
+  return SCL_OK;
+}
+
+// An operand addressed with several strides, as span.hpp sees it: ONE row of its bounding extent
+// sum_j (count_j - 1) stride_j + N elements.  false: the extent does not fit size_t.
+bool extent_of(std::initializer_list<std::pair<size_t, size_t>> dims, size_t N, size_t* out) {
+  size_t e = N;
+  for (const auto& d : dims) {
+    size_t part = 0;
+    if (d.first == 0) continue;
+    if (__builtin_mul_overflow(d.first - 1, d.second, &part) || __builtin_add_overflow(e, part, &e)) return false;
+  }
+  *out = e;
+  return true;
+}
+
+// ---- the pack kernels (unit_device.hpp: for_each_pack) ----
 // two one-limb elements per lane: every base 16-byte aligned, every stride that separates rows or terms even
 bool two_per_lane(size_t limbs, std::initializer_list<const void*> ptrs, std::initializer_list<size_t> strides) {
   if (limbs != 1) return false;
@@ -172,6 +210,41 @@ bool two_per_lane(size_t limbs, std::initializer_list<const void*> ptrs, std::in
   return true;
 }
 
+// blocks along x for a row of N elements: one lane per pair and one for the odd element after the last pair, or one per element
+unsigned grid_for_packs(bool two, size_t N) { return grid_for(two ? N / 2 + (N & 1) : N); }
+
+// Launch a pack kernel, KERNEL<F, VEC, further template arguments...> with VEC = 2 where `TWO` (what two_per_lane said) and 1
+// elsewhere, on GRID -- dim3(grid_for_packs(TWO, N), rows, ...) -- with the remaining arguments.  KSPEC names the kernel in
+// parentheses, (KERNEL, F) or (KERNEL, F, further...).  The two-per-lane form exists for the one-limb fields only.  As in
+//   PACK_LAUNCH((k_hm_mask, F), two, dim3(grid_for_packs(two, N), (unsigned)rows), S(stream), ctx, d, d_stride, x, y, r2, op_stride, N);
+//   PACK_LAUNCH((k_hm_apply, F, R), two, dim3(grid_for_packs(two, N), nb, ng), S(stream), ctx, ...);   // k_hm_apply<F, VEC, R>
+// (KSPEC is taken apart by the helper macros below; with no further arguments the comma before them goes by the compilers'
+// `, ##__VA_ARGS__`.  A KSPEC without its parentheses fails in the helpers' expansion, not at the kernel's name.)
+#define PACK_KERNEL_(VEC, KERNEL, F, ...) KERNEL<F, VEC, ##__VA_ARGS__>
+#define PACK_KERNEL_2_(...) PACK_KERNEL_(2, __VA_ARGS__)
+#define PACK_KERNEL_1_(...) PACK_KERNEL_(1, __VA_ARGS__)
+#define PACK_FIELD_(KERNEL, F, ...) F
+#define PACK_LAUNCH(KSPEC, TWO, GRID, ST, ...)                                                        \
+  do {                                                                                                \
+    bool one_ = true;                                                                                 \
+    if constexpr (PACK_FIELD_ KSPEC::LIMBS == 1) {                                                    \
+      if (TWO) {                                                                                      \
+        hipLaunchKernelGGL((PACK_KERNEL_2_ KSPEC), GRID, dim3(BLOCK), 0, ST, __VA_ARGS__);            \
+        one_ = false;                                                                                 \
+      }                                                                                               \
+    }                                                                                                 \
+    if (one_) hipLaunchKernelGGL((PACK_KERNEL_1_ KSPEC), GRID, dim3(BLOCK), 0, ST, __VA_ARGS__);      \
+    HIP_TRY(hipGetLastError());                                                                       \
+  } while (0)
+
+// the recombination vector of an opening inside a finish kernel (m <= OPEN_M_MAX, which the entry point has checked)
+template <class F>
+OpenTable<F> make_open_table(const uint64_t* lambda_host, size_t m) {
+  OpenTable<F> tab;
+  for (size_t j = 0; j < (size_t)OPEN_M_MAX; ++j) tab.v[j] = j < m ? F::ld(lambda_host + j * F::LIMBS) : F::zero();
+  return tab;
+}
+
 }  // namespace
 #endif  // !SCL_UNIT_ENGINE
 
@@ -180,6 +253,22 @@ bool two_per_lane(size_t limbs, std::initializer_list<const void*> ptrs, std::in
 #include "aes_key_host.hpp"  // make_aes_key
 
 namespace {
+
+// ---- the dealers (prg_deal.hpp) ----
+constexpr size_t PARTY_MAX = 65535;  // the node i + 1 as a small integer (GF(2^128): F::muladd_small takes 16 bits)
+// The largest degree the two-pass path of a dealer takes: beyond it scl_hip_shamir_share evaluates chunk by chunk, staging each
+// chunk's power table from host memory and synchronising the stream before it returns -- a call of these libraries never
+// synchronises
+constexpr size_t DEG_MAX_NARROW = 48;  // 8- and 16-byte elements
+constexpr size_t DEG_MAX_WIDE = 16;    // 32-byte elements
+size_t deg_max(size_t limbs) { return limbs == 4 ? DEG_MAX_WIDE : DEG_MAX_NARROW; }
+
+// N * B blocks from counter0 (and the slack aes_key_range adds) must not wrap the 64-bit counter
+int check_counter_range(const std::string& who, uint64_t counter0, size_t N, uint64_t B) {
+  const uint64_t room = ~(uint64_t)0 - 128;
+  if (counter0 > room || N > (room - counter0) / B) return fail(SCL_ERR_BAD_ARG, who + ": the block range wraps the 64-bit counter");
+  return SCL_OK;
+}
 
 unsigned grid_aes4(size_t work_items) {  // one 1024-lane workgroup per CU; the kernels grid-stride
   const size_t blocks = (work_items + sclhip::ABLOCK - 1) / sclhip::ABLOCK;

@@ -80,7 +80,8 @@ struct CoeffRows {
 
 // ... or the AES-CTR stream: repetition j is Vector::random(N) at block counter0 + j B, and pack q of a Mersenne61 vector is
 // block q (the low and the high 8 bytes), element q of a 16-byte field block q, of a 32-byte field blocks 2q and 2q + 1
-// (k_vector_random).  Packs past N draw blocks past the vector's: they meet zeros of x.
+// (k_vector_random).  Packs past N draw blocks past the vector's: they meet zeros of x.  (The dealers' order, one secret's
+// polynomials after another, is another one: csrc/prg_deal.hpp.)
 template <class F>
 struct CoeffPrg {
   const typename F::Ctx& ctx;
@@ -103,7 +104,7 @@ struct CoeffPrg {
         }
       } else {
         // two blocks abreast: left alone the compiler runs all REPS * U draws abreast and runs out of the 128 registers a
-        // 1024-lane workgroup has (as csrc/hm_unit.hip's draw_poly).  The empty statement makes the next pair's counters wait
+        // 1024-lane workgroup has (as csrc/prg_deal.hpp's draw_poly).  The empty statement makes the next pair's counters wait
         // for this pair's result.
         constexpr int NB = U < 2 ? U : 2;
 #pragma unroll

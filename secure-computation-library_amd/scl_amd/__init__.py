@@ -70,9 +70,16 @@ class SclError(RuntimeError):
         super().__init__(f"[{status}] {self.reference_message}" + (f" ({detail})" if detail and detail != self.reference_message else ""))
 
 
-def _chk(status: int):
-    if status != OK:
-        raise SclError(status, lib.scl_hip_last_error().decode())
+def _checker(last_error_fn):
+    """the status check of one library: raises SclError with the diagnostic of that library's own slot (an extension library
+    beside the engine keeps its own: `_chk = _scl._checker(lib.scl_X_last_error)`)"""
+    def chk(status: int):
+        if status != OK:
+            raise SclError(status, last_error_fn().decode())
+    return chk
+
+
+_chk = _checker(lib.scl_hip_last_error)
 
 
 def limbs(field: int) -> int:
@@ -121,6 +128,27 @@ def _dev_rows(t: torch.Tensor):
               (rows > 1 and (t.stride(0) % L or t.stride(0) < N * L))):
         raise SclError(ERR_BAD_ARG, "share matrix rows must be dense (a row pitch is allowed)")
     return C.c_void_p(t.data_ptr()), (t.stride(0) // L if rows > 1 else max(N, 1))
+
+
+def _rows3(field, t: torch.Tensor, what: str):
+    """an operand as [rows][N][L]: a vector [N][L] is one row"""
+    L = limbs(field)
+    if t.dtype != torch.int64:
+        raise SclError(ERR_BAD_ARG, f"{what}: dtype {t.dtype}, expected int64 limbs")
+    if t.dim() == 2:
+        t = t.unsqueeze(0)
+    if t.dim() != 3 or t.shape[2] != L:
+        raise SclError(ERR_SIZE_MISMATCH, f"{what}: shape {tuple(t.shape)}, expected [rows][N][{L}] or [N][{L}]")
+    return t
+
+
+def _status(N: int, like: torch.Tensor, status, what: str):
+    """the status bytes of a call, one per column: the caller's buffer checked, or a new one beside `like`"""
+    if status is None:
+        return torch.empty(N, dtype=torch.uint8, device=like.device)
+    if status.dtype != torch.uint8 or tuple(status.shape) != (N,) or status.device != like.device or not status.is_contiguous():
+        raise SclError(ERR_SIZE_MISMATCH, f"{what}: status must be a contiguous uint8 tensor of {N} bytes on {like.device}")
+    return status
 
 
 def _host(a) -> np.ndarray:

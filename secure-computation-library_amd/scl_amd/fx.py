@@ -28,26 +28,12 @@ STATUS_OK, STATUS_RANGE = 0, 1
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_fx.h", "scl_fx_", "SCL_FX_ABI_VERSION", "scl_amd.fx")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_fx_last_error().decode())
+_chk = _scl._checker(lib.scl_fx_last_error)
 
 
 def max_bits(field) -> int:
     """|p| - 2, the largest bit count B (scl_fx_max_bits); 0 for a tag the library refuses"""
     return int(lib.scl_fx_max_bits(field))
-
-
-def _rows3(field, t: torch.Tensor, what: str):
-    """an operand as [rows][N][L]: a vector [N][L] is one row"""
-    L = _scl.limbs(field)
-    if t.dtype != torch.int64:
-        raise _scl.SclError(_scl.ERR_BAD_ARG, f"{what}: dtype {t.dtype}, expected int64 limbs")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.dim() != 3 or t.shape[2] != L:
-        raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{what}: shape {tuple(t.shape)}, expected [rows][N][{L}] or [N][{L}]")
-    return t
 
 
 def _planes(field, bits: torch.Tensor, rows, N, like, what: str):
@@ -68,14 +54,6 @@ def _planes(field, bits: torch.Tensor, rows, N, like, what: str):
     return C.c_void_p(bits.data_ptr()), (bits.stride(0) // L if B > 1 else max(n, 1)), (bits.stride(1) // L if R > 1 else max(n, 1)), B
 
 
-def _status(N: int, like: torch.Tensor, status, what: str):
-    if status is None:
-        return torch.empty(N, dtype=torch.uint8, device=like.device)
-    if status.dtype != torch.uint8 or tuple(status.shape) != (N,) or status.device != like.device or not status.is_contiguous():
-        raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{what}: status must be a contiguous uint8 tensor of {N} bytes on {like.device}")
-    return status
-
-
 def compose(field, bits, out=None):
     """out[r][s] = sum_i 2^i bits[i][r][s] (scl_fx_compose): bits [B][rows][N][L] (or [B][N][L]: one row) -> [rows][N][L] (or
     [N][L])."""
@@ -83,7 +61,7 @@ def compose(field, bits, out=None):
     one_row = bits.dim() == 3
     pb, ps, rs, B = _planes(field, bits, None, None, None, "compose bits")
     rows, N = (1, bits.shape[1]) if one_row else (bits.shape[1], bits.shape[2])
-    o = torch.empty(rows, N, L, dtype=torch.int64, device=bits.device) if out is None else _rows3(field, out, "compose out")
+    o = torch.empty(rows, N, L, dtype=torch.int64, device=bits.device) if out is None else _scl._rows3(field, out, "compose out")
     _scl._want(o, (rows, N, L), "compose out", bits)
     po, so = _scl._dev_rows(o)
     _chk(lib.scl_fx_compose(field, po, C.c_size_t(so), pb, C.c_size_t(ps), C.c_size_t(rs), C.c_size_t(B), C.c_size_t(rows), C.c_size_t(N), _scl._stream()))
@@ -95,11 +73,11 @@ def compose(field, bits, out=None):
 def trunc_mask(field, x, bits, k: int, shift: int, out=None, rlow=None):
     """(c, rlow): c = x + 2^(k-1) + r and rlow = r', r = sum_{i<B} 2^i bits[i], r' its lowest `shift` planes, in one launch
     (scl_fx_trunc_mask).  x [rows][N][L] (or [N][L]: one row), bits [B][rows][N][L] (or [B][N][L]); `out` may be x (in place)."""
-    X = _rows3(field, x, "trunc_mask x")
+    X = _scl._rows3(field, x, "trunc_mask x")
     rows, N, L = X.shape
     pb, ps, rs, B = _planes(field, bits, rows, N, X, "trunc_mask bits")
-    c = torch.empty(rows, N, L, dtype=torch.int64, device=X.device) if out is None else _rows3(field, out, "trunc_mask out")
-    lo = torch.empty(rows, N, L, dtype=torch.int64, device=X.device) if rlow is None else _rows3(field, rlow, "trunc_mask rlow")
+    c = torch.empty(rows, N, L, dtype=torch.int64, device=X.device) if out is None else _scl._rows3(field, out, "trunc_mask out")
+    lo = torch.empty(rows, N, L, dtype=torch.int64, device=X.device) if rlow is None else _scl._rows3(field, rlow, "trunc_mask rlow")
     _scl._want(c, (rows, N, L), "trunc_mask out", X)
     _scl._want(lo, (rows, N, L), "trunc_mask rlow", X)
     (pc, sc), (pl, sl), (px, sx) = _scl._dev_rows(c), _scl._dev_rows(lo), _scl._dev_rows(X)
@@ -116,7 +94,7 @@ def trunc_finish(field, csh, x, rlow, shift: int, B: int, lam=None, out=None, st
     that column is 0 in every row.  `out` may be x or rlow (in place)."""
     from scl_amd import hm
     L = _scl.limbs(field)
-    D, X, R = _rows3(field, csh, "trunc_finish csh"), _rows3(field, x, "trunc_finish x"), _rows3(field, rlow, "trunc_finish rlow")
+    D, X, R = _scl._rows3(field, csh, "trunc_finish csh"), _scl._rows3(field, x, "trunc_finish x"), _scl._rows3(field, rlow, "trunc_finish rlow")
     m, N, _ = D.shape
     rows = X.shape[0]
     _scl._want(X, (rows, N, L), "trunc_finish x", D)
@@ -124,9 +102,9 @@ def trunc_finish(field, csh, x, rlow, shift: int, B: int, lam=None, out=None, st
     if lam is None:
         lam = hm.element(field, 1)[None] if csh.dim() == 2 else _scl.lagrange_basis(field, m)
     lam = _scl._host(lam).reshape(m, L)
-    y = torch.empty(rows, N, L, dtype=torch.int64, device=D.device) if out is None else _rows3(field, out, "trunc_finish out")
+    y = torch.empty(rows, N, L, dtype=torch.int64, device=D.device) if out is None else _scl._rows3(field, out, "trunc_finish out")
     _scl._want(y, (rows, N, L), "trunc_finish out", D)
-    st = _status(N, D, status, "trunc_finish")
+    st = _scl._status(N, D, status, "trunc_finish")
     (py, sy), (pd, sd), (px, sx), (pr, sr) = _scl._dev_rows(y), _scl._dev_rows(D), _scl._dev_rows(X), _scl._dev_rows(R)
     _chk(lib.scl_fx_trunc_finish(field, py, C.c_size_t(sy), C.c_void_p(st.data_ptr()), pd, C.c_size_t(sd), _scl._hp(lam), C.c_size_t(m), px, C.c_size_t(sx),
                                  pr, C.c_size_t(sr), C.c_size_t(shift), C.c_size_t(B), C.c_size_t(rows), C.c_size_t(N), _scl._stream()))

@@ -26,9 +26,7 @@ TWO_PASS = 1                # flags bit 0 of double_share
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_hm.h", "scl_hm_", "SCL_HM_ABI_VERSION", "scl_amd.hm")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_hm_last_error().decode())
+_chk = _scl._checker(lib.scl_hm_last_error)
 
 
 def double_blocks(field, n: int, t: int) -> int:
@@ -150,22 +148,10 @@ def apply_matrix(field, M, x, out=None):
     return out
 
 
-def _rows3(field, t: torch.Tensor, what: str):
-    """an operand as [rows][N][L]: a vector [N][L] is one row"""
-    L = _scl.limbs(field)
-    if t.dtype != torch.int64:
-        raise _scl.SclError(_scl.ERR_BAD_ARG, f"{what}: dtype {t.dtype}, expected int64 limbs")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.dim() != 3 or t.shape[2] != L:
-        raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{what}: shape {tuple(t.shape)}, expected [rows][N][{L}] or [N][{L}]")
-    return t
-
-
 def mul_mask(field, x, y, r2, out=None):
     """[d]_2t = [x]_t [y]_t + [R]_2t, one product and one reduction per element (scl_hm_mul_mask).  Operands [rows][N][L] (or
     [N][L]: one row) of one row stride; `out` may be r2 (in place)."""
-    ops = [(nm, _rows3(field, t, "mul_mask " + nm)) for nm, t in (("x", x), ("y", y), ("r2", r2))]
+    ops = [(nm, _scl._rows3(field, t, "mul_mask " + nm)) for nm, t in (("x", x), ("y", y), ("r2", r2))]
     rows, N, L = ops[0][1].shape
     ptrs, stride = [], None
     for nm, t in ops:
@@ -175,7 +161,7 @@ def mul_mask(field, x, y, r2, out=None):
             raise _scl.SclError(_scl.ERR_BAD_ARG, f"mul_mask {nm}: row stride {s}, x has {stride} (operands share op_stride)")
         stride = s
         ptrs.append(p)
-    d = torch.empty(rows, N, L, dtype=torch.int64, device=x.device) if out is None else _rows3(field, out, "mul_mask out")
+    d = torch.empty(rows, N, L, dtype=torch.int64, device=x.device) if out is None else _scl._rows3(field, out, "mul_mask out")
     _scl._want(d, (rows, N, L), "mul_mask out", ops[0][1])
     pd, sd = _scl._dev_rows(d)
     _chk(lib.scl_hm_mul_mask(field, pd, C.c_size_t(sd), *ptrs, C.c_size_t(stride), C.c_size_t(rows), C.c_size_t(N), _scl._stream()))
@@ -189,14 +175,14 @@ def mul_finish(field, dsh, r, lam=None, out=None):
     opened), lam their Lagrange basis (default: nodes 1..m at 0; for an opened d: one), r [rows][N][L] (or [N][L]: one row).
     `out` may be r (in place)."""
     L = _scl.limbs(field)
-    D, R = _rows3(field, dsh, "mul_finish dsh"), _rows3(field, r, "mul_finish r")
+    D, R = _scl._rows3(field, dsh, "mul_finish dsh"), _scl._rows3(field, r, "mul_finish r")
     m, N, _ = D.shape
     rows = R.shape[0]
     _scl._want(R, (rows, N, L), "mul_finish r", D)
     if lam is None:
         lam = element(field, 1)[None] if dsh.dim() == 2 else _scl.lagrange_basis(field, m)
     lam = _scl._host(lam).reshape(m, L)
-    z = torch.empty(rows, N, L, dtype=torch.int64, device=D.device) if out is None else _rows3(field, out, "mul_finish out")
+    z = torch.empty(rows, N, L, dtype=torch.int64, device=D.device) if out is None else _scl._rows3(field, out, "mul_finish out")
     _scl._want(z, (rows, N, L), "mul_finish out", D)
     (pz, sz), (pd, sd), (pr, sr) = _scl._dev_rows(z), _scl._dev_rows(D), _scl._dev_rows(R)
     _chk(lib.scl_hm_mul_finish(field, pz, C.c_size_t(sz), pd, C.c_size_t(sd), _scl._hp(lam), C.c_size_t(m), pr, C.c_size_t(sr),

@@ -23,9 +23,7 @@ lib, _SO = _abi.load("scl_hip_ip")
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_ip.h", "scl_ip_", "SCL_IP_ABI_VERSION", "scl_amd.ip")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_ip_last_error().decode())
+_chk = _scl._checker(lib.scl_ip_last_error)
 
 
 def matmul_tile(field):

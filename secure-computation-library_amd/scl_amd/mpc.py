@@ -21,21 +21,7 @@ lib, _SO = _abi.load("scl_hip_mpc")
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_mpc.h", "scl_mpc_", "SCL_MPC_ABI_VERSION", "scl_amd.mpc")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_mpc_last_error().decode())
-
-
-def _rows3(field, t: torch.Tensor, what: str):
-    """an operand as [rows][N][L]: a vector [N][L] is one row"""
-    L = _scl.limbs(field)
-    if t.dtype != torch.int64:
-        raise _scl.SclError(_scl.ERR_BAD_ARG, f"{what}: dtype {t.dtype}, expected int64 limbs")
-    if t.dim() == 2:
-        t = t.unsqueeze(0)
-    if t.dim() != 3 or t.shape[2] != L:
-        raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{what}: shape {tuple(t.shape)}, expected [rows][N][{L}] or [N][{L}]")
-    return t
+_chk = _scl._checker(lib.scl_mpc_last_error)
 
 
 def _same_rows(field, named):
@@ -61,7 +47,7 @@ def beaver_mask(field, x, y, a, b, out=None):
     with one row the tensor is the reference's packet, e then d; with rows = n the halves go to shamir_recover /
     additive_recover as they lie."""
     vec = x.dim() == 2
-    ops = [(n, _rows3(field, t, "beaver_mask " + n)) for n, t in (("x", x), ("y", y), ("a", a), ("b", b))]
+    ops = [(n, _scl._rows3(field, t, "beaver_mask " + n)) for n, t in (("x", x), ("y", y), ("a", a), ("b", b))]
     rows, N, L = ops[0][1].shape
     ptrs, stride = _same_rows(field, ops)
     if out is None:
@@ -78,7 +64,7 @@ def beaver_finish(field, e, d, a, b, c, ed_rows, out=None):
     a, b, c: [rows][N][L] (or [N][L]: one row).  Shamir: ed_rows = rows; additive: 1 where row 0 is party 0, else 0.  `out` may be
     a, b or c (in place)."""
     vec = a.dim() == 2
-    ops = [(n, _rows3(field, t, "beaver_finish " + n)) for n, t in (("a", a), ("b", b), ("c", c))]
+    ops = [(n, _scl._rows3(field, t, "beaver_finish " + n)) for n, t in (("a", a), ("b", b), ("c", c))]
     rows, N, L = ops[0][1].shape
     _scl._want(e, (N, L), "beaver_finish e", a)
     _scl._want(d, (N, L), "beaver_finish d", a)
@@ -86,7 +72,7 @@ def beaver_finish(field, e, d, a, b, c, ed_rows, out=None):
     if out is None:
         z = torch.empty(rows, N, L, dtype=torch.int64, device=a.device)
     else:
-        z = _rows3(field, out, "beaver_finish out")
+        z = _scl._rows3(field, out, "beaver_finish out")
         _scl._want(z, (rows, N, L), "beaver_finish out", a)
     pz, sz = _scl._dev_rows(z)
     _chk(lib.scl_mpc_beaver_finish(field, pz, C.c_size_t(sz), _scl._dev(e), _scl._dev(d), *ptrs, C.c_size_t(stride), C.c_size_t(rows),

@@ -25,9 +25,7 @@ TWO_PASS = 1                # flags bit 0 of deal_triples_shamir
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_prep.h", "scl_prep_", "SCL_PREP_ABI_VERSION", "scl_amd.prep")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_prep_last_error().decode())
+_chk = _scl._checker(lib.scl_prep_last_error)
 
 
 def triple_blocks(field, scheme: int, n: int, t: int = 0) -> int:

@@ -27,17 +27,7 @@ STATUS_OK, STATUS_ZERO, STATUS_NONRESIDUE = 0, 1, 2
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_rb.h", "scl_rb_", "SCL_RB_ABI_VERSION", "scl_amd.rb")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_rb_last_error().decode())
-
-
-def _status(N: int, like: torch.Tensor, status, what: str):
-    if status is None:
-        return torch.empty(N, dtype=torch.uint8, device=like.device)
-    if status.dtype != torch.uint8 or tuple(status.shape) != (N,) or status.device != like.device or not status.is_contiguous():
-        raise _scl.SclError(_scl.ERR_SIZE_MISMATCH, f"{what}: status must be a contiguous uint8 tensor of {N} bytes on {like.device}")
-    return status
+_chk = _scl._checker(lib.scl_rb_last_error)
 
 
 def sqrt(field, a, flags: int = 0, out=None, status=None):
@@ -48,7 +38,7 @@ def sqrt(field, a, flags: int = 0, out=None, status=None):
     N = a.shape[0]
     _scl._want(a, (N, L), "sqrt a")
     out = torch.empty_like(a) if out is None else _scl._want(out, (N, L), "sqrt out", a)
-    st = _status(N, a, status, "sqrt")
+    st = _scl._status(N, a, status, "sqrt")
     _chk(lib.scl_rb_sqrt(field, _scl._dev(out), C.c_void_p(st.data_ptr()), _scl._dev(a), C.c_size_t(N), C.c_uint(flags), _scl._stream()))
     return out, st
 
@@ -68,7 +58,7 @@ def bits_finish(field, u, r, out=None, status=None):
         B = torch.empty(rows, N, L, dtype=torch.int64, device=R.device)
     else:
         B = _scl._want(out.unsqueeze(0) if out.dim() == 2 else out, (rows, N, L), "bits_finish out", R)
-    st = _status(N, R, status, "bits_finish")
+    st = _scl._status(N, R, status, "bits_finish")
     (pb, sb), (pr, sr) = _scl._dev_rows(B), _scl._dev_rows(R)
     _chk(lib.scl_rb_bits_finish(field, pb, C.c_size_t(sb), C.c_void_p(st.data_ptr()), _scl._dev(u), pr, C.c_size_t(sr), C.c_size_t(rows),
                                 C.c_size_t(N), _scl._stream()))

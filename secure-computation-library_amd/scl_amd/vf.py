@@ -28,9 +28,7 @@ REPS_MAX = 4
 _NPROTO = _abi.declare(lib, _SO, "scl_hip_vf.h", "scl_vf_", "SCL_VF_ABI_VERSION", "scl_amd.vf")
 
 
-def _chk(status: int):
-    if status != _scl.OK:
-        raise _scl.SclError(status, lib.scl_vf_last_error().decode())
+_chk = _scl._checker(lib.scl_vf_last_error)
 
 
 def coin_blocks(field, N: int) -> int:

@@ -2,9 +2,9 @@
 
 Parity: both calls word for word against the same values composed from the oracle's element-wise calls (O.Port().ew) on identical
 PRG-seeded inputs, at the smallest shapes where the pack / tail / per-row logic can go wrong -- N one either side of a wavefront
-and of a block's pairs, an odd N behind the two-per-lane body, more than one block; one row and three; dense rows and a pitch of
-N + 5 (odd for even N: the one-per-lane form of the one-limb fields); for the one-limb fields also a base 8 bytes past a 16-byte
-boundary.  Extremes: operands from extremes.pool against extremes.Model's integer arithmetic, a second and independent statement
+and of a block's pairs, one pair and no tail (2), 256 pairs and the tail in lane 0 of the next block (513), an odd N behind the
+two-per-lane body, more than one block; one row and three; dense rows and a pitch of N + 5 (odd for even N: the one-per-lane
+form of the one-limb fields); for the one-limb fields also a base 8 bytes past a 16-byte boundary.  Extremes: operands from extremes.pool against extremes.Model's integer arithmetic, a second and independent statement
 of the result.  Aliasing, the protocol end to end between existing entry points (Shamir and additive, all parties at once and
 party by party), capture into one graph, and the C++ mirror's round trips.
 
@@ -27,7 +27,7 @@ pytestmark = pytest.mark.gpu
 FIELDS = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
 TAGS = FIELDS + [O.Z2K(K) for K in X.RING_BITS]
 PRIME_FIELDS = [O.M61, O.M127, O.MONT128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]
-NS = [1, 63, 64, 65, 255, 4099]
+NS = [1, 2, 63, 64, 65, 255, 257, 513, 4099]
 ROWS = [1, 3]
 NMAX, RMAX = max(NS), max(ROWS)
 assert (RMAX, NMAX) == (BEAVER_ROWS, BEAVER_N)          # the shape of the shared reference (tests/gpu_support.py)

@@ -62,16 +62,17 @@ def dot_reference(scl, port, f):
 # ---- dot ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("f", FIELDS, ids=fname)
 def test_dot_equals_the_model(env, f):
-    """terms 1, 2, 7, 64, 65 x rows 1, 10 x N 1, 2, 3, 64, 257, 1025 x the three row pitches (x the two base phases for the
-    one-limb field: 8 bytes past a 16-byte boundary is the one-column fallback, an even pitch at phase 0 the two-column path with
-    its tail lane at odd N), and an odd term stride at N = 3 and 257: with r2, without it and in place on r2; the inputs are
-    unchanged, the gaps between rows unwritten; terms == 1 is hm.mul_mask on the same buffers"""
+    """terms 1, 2, 7, 64, 65 x rows 1, 10 x N 1, 2, 3, 64, 257, 1025 (the one-limb field also 513: 256 pairs fill block 0 and the
+    tail is lane 0 of block 1) x the three row pitches (x the two base phases for the one-limb field: 8 bytes past a 16-byte
+    boundary is the one-column fallback, an even pitch at phase 0 the two-column path with its tail lane at odd N), and an odd
+    term stride at N = 3 and 257: with r2, without it and in place on r2; the inputs are unchanged, the gaps between rows
+    unwritten; terms == 1 is hm.mul_mask on the same buffers"""
     scl, hm, ip, port = env
     xd, yd, rd, want = dot_reference(scl, port, f)
     for terms in TERMS:
         w0, w1 = want[terms]
         for rows in ROWS:
-            for N in NS:
+            for N in (sorted(NS + [513]) if O.LIMBS[f] == 1 else NS):
                 x, y, r = xd[:terms, :rows, :N], yd[:terms, :rows, :N], rd[:rows, :N]
                 cases = [(p, ph, 0) for p in pitches(f, N) for ph in ((0, 1) if O.LIMBS[f] == 1 else (0,))]
                 if N in (3, 257):

@@ -110,13 +110,14 @@ def bits_case(env, f, mp, p, rows, N, pitch, tag):
 
 @pytest.mark.parametrize("name,f,mp", CASES, ids=IDS)
 def test_bits_finish_equals_the_model(env, modulus, name, f, mp):
-    """rows in {1, 3, 10}, row strides N and N + 3, N in {1, 65, 257}: a planted u = 0 and a planted non-residue carry their
-    status and a column of zeros; Mersenne61 also at 17 rows (past the rows whose loads are issued before the chain); its odd
-    strides take one column per lane, its even ones two"""
+    """rows in {1, 3, 10}, row strides N and N + 3, N in {1, 65, 257} (Mersenne61 also 2, one pair and no tail, and 513, 256 pairs
+    and the tail in lane 0 of the next block): a planted u = 0 and a planted non-residue carry their status and a column of
+    zeros; Mersenne61 also at 17 rows (past the rows whose loads are issued before the chain); its odd strides take one column
+    per lane, its even ones two"""
     mp = modulus(mp)
     p = RBS.prime(f, mp)
     tag = 100 * IDS.index(name)
-    for N in (1, 65, 257):
+    for N in (1, 65, 257) + ((2, 513) if f == O.M61 else ()):
         for rows in (1, 3, 10) + ((17,) if f == O.M61 else ()):
             for pitch in (N, N + 3):
                 bits_case(env, f, mp, p, rows, N, pitch, tag + rows)
