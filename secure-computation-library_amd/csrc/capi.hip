@@ -37,331 +37,50 @@ hipError_t gemm_launch_main(u64* C, size_t ldc, const u64x2* Ap, const u64x2* Bp
 
 using namespace sclhip;
 
-// ---- state shared by the translation units of the library ------------------------------------------------
-// The library is this file compiled once per field family (tu_config.hpp, Makefile); the unit built with SCL_TU_COMMON
-// defines the state below, the others see it as extern.  Everything mutable is per host thread except the Mont128 default
-// (behind its mutex).
-struct Knob {
-  long v;
-  long load() const { return v; }
-  Knob& operator=(long x) {
-    v = x;
-    return *this;
-  }
-};
-struct Scratch {
-  int device = -1;
-  void* dev = nullptr;
-  size_t bytes = 0;
-};
-struct TempArena {
-  int device = -1;
-  void* dev = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
-};
-namespace sclhip_state {
+// The state the units of the library share, the Mont128 latch, with_field and the per-thread buffers (and with them fail /
+// HIP_TRY / SCL_TRY / S / aligned16 / alias_check of unit_host.hpp): engine_state.hpp.  The common unit defines the state.
 #if SCL_TU_COMMON
-#define SCL_STATE(decl, ...) decl __VA_ARGS__
-#else
-#define SCL_STATE(decl, ...) extern decl
+#define SCL_ENGINE_STATE_DEFINE
 #endif
-SCL_STATE(thread_local std::string g_err);
-// Experiment knobs (scl_hip_set_tuning).  Per host thread, like the Mont128 modulus below: the library keeps no mutable
-// state that two host threads share, so concurrent callers with different settings cannot race (scl_hip.h, Conventions).
-SCL_STATE(thread_local Knob g_max_blocks, {0});
-SCL_STATE(thread_local Knob g_force_scalar, {0});
-SCL_STATE(thread_local Knob g_force_table, {0});
-SCL_STATE(thread_local Knob g_mfma, {0});       // 0 auto, 1 always (where applicable), -1 never
-// GF(2^128) sharing at the default nodes: 1 = eight nodes per Horner loop (k_share_gf_tiles), 0 = one node at a time
-// (k_share_gf_nodes) ("gf_tiles")
-SCL_STATE(thread_local Knob g_gf_tiles, {1});
-SCL_STATE(thread_local Knob g_open_gather_always, {0});  // the open step on ONE rank: 1 = still through RCCL's all-gather
-SCL_STATE(thread_local Knob g_prg_two_pass, {0});  // PRG-driven sharing: 0 auto, 1 always two passes, -1 always fused
-// Headline streaming kernels (k_recover_fixed, k_share_small): resident waves per CU (kernels.hpp, "Launch geometry");
-// "stream_waves" 0 = no cap, -1 = by element size: 10 for one-word elements, 12 for wider ones (profiles/r2_probe_cap_rec.txt,
-// r2_probe_c3_waves.txt)
-SCL_STATE(thread_local Knob g_stream_waves, {-1});
-// the same cap for the Mersenne61 small-node share kernel ("share_waves"; 0 = the 256-thread kernel without a cap)
-SCL_STATE(thread_local Knob g_share_waves, {9});
-SCL_STATE(thread_local Knob g_share_waves128, {12});  // .. and for the 16-byte fields' small-node share kernel ("share_waves128")
-SCL_STATE(thread_local Knob g_aes_blocks, {0});
-// element-wise inverse / divide: 0 auto = Montgomery's simultaneous inversion with the chain length chosen by the batch, N > 0 =
-// that chain length (8, 16, 32, 64 or 128; Mersenne61: any N = its register kernel), -1 = one Fermat chain per element (k_ew, the kernels
-// of rounds 1-4); GF(2^128) multiply: -1 = the register-only product ("inv_batch")
-SCL_STATE(thread_local Knob g_inv_batch, {0});
-SCL_STATE(thread_local Knob g_inv_two_level, {0});
-SCL_STATE(thread_local Knob g_gemm_slab_mib, {0});  // digit planes per factor and launch of the general matrix-core product, MiB (0 = 1024) ("gemm_slab_mib")
-SCL_STATE(thread_local Knob g_matmul_lds_min, {0});  // columns from which k_matmul (left factor in LDS, a thread per column) is taken; thin kernel likewise (0 = default) ("matmul_lds_min")
-SCL_STATE(thread_local Knob g_transpose_tile, {0});  // secrets per LDS tile of the 16-byte layout bridge (0 = 512 within 40 KiB) ("transpose_tile")
-// Mont128 modulus: a process-wide default, latched per host thread at its first use (mont_ctx below)
-SCL_STATE(thread_local Mont128::Ctx g_mont, = {0, 0, 0, 0});  // p == 0: this thread has not latched a modulus yet
-SCL_STATE(std::mutex g_mont_default_mu);
-SCL_STATE(Mont128::Ctx g_mont_default, = {0, 0, 0, 0});
-// how often the default has been set, and where this thread stands: the generation it latched (or set its own modulus) at
-SCL_STATE(unsigned long g_mont_default_gen, = 0);
-SCL_STATE(thread_local unsigned long g_mont_gen, = 0);
-SCL_STATE(thread_local bool g_mont_own, = false);
-// per-thread device scratch (only used by calls that synchronise before returning)
-SCL_STATE(thread_local Scratch g_scratch);
-// the "a zero was inverted" flag of scl_hip_ew in pinned host memory the device writes straight into: the call then needs no
-// memset launch and no copy back, only the stream synchronisation it owes its caller anyway.  host == nullptr: not allocated
-// (yet, or the allocation failed once: then the flag lives in the device scratch as before)
-struct HostFlag {
-  unsigned* host = nullptr;
-  unsigned* dev = nullptr;
-  bool failed = false;
-};
-SCL_STATE(thread_local HostFlag g_hflag);
-// arena 0: tables, queues and products of one call; arena 1: the coefficient rows of a two-pass PRG sharing (whose second
-// pass may take arena 0 itself)
-SCL_STATE(thread_local TempArena g_temps[2]);
-#undef SCL_STATE
-}  // namespace sclhip_state
-using namespace sclhip_state;
-
-// fail / HIP_TRY / SCL_TRY / S / aligned16 / alias_check on the slot above, and make_aes_key: shared with the other units.
-// (The launch helpers of unit_host.hpp's other parts are not taken: grid_for, grid_aes4 and AES4_LAUNCH below honour the
-// "max_blocks" / "aes_blocks" knobs.)
-#define SCL_UNIT_ENGINE
-#include "unit_host.hpp"
+#include "engine_state.hpp"
+#include "launch_rules.hpp"
 #include "aes_key_host.hpp"
 
 namespace {
 
-// dynamic LDS bytes that cap the residency of a kernel with `static_lds` bytes of its own at `waves` waves of
-// `block` threads per CU.  A CU has 160 KiB of LDS and hands it out in granules; the granule of gfx950 is not documented
-// (512 B on earlier parts, 1280 B = 1/128 of the array is the other candidate), so the request is chosen to hold for BOTH:
-// `groups` allocations fit, `groups + 1` do not, whichever granule rounds it up.  No such size exists for every count
-// (24 and more groups per CU): then no cap is applied.
-size_t residency_pad(long waves, int block, size_t static_lds) {
-  if (waves <= 0) return 0;
-  const size_t groups = (size_t)(waves * 64 / block);
-  if (groups < 1) return 0;
-  constexpr size_t LDS = 160 * 1024;
-  auto holds = [&](size_t total, size_t granule) {
-    const size_t alloc = (total + granule - 1) / granule * granule;
-    return groups * alloc <= LDS && (groups + 1) * alloc > LDS;
-  };
-  for (size_t total = LDS / groups / 128 * 128; total > static_lds && total >= 1024; total -= 128)
-    if (holds(total, 512) && holds(total, 1280)) return total <= 64 * 1024 ? total - static_lds : 0;
-  return 0;
-}
-
-unsigned grid_for(size_t work_items) {
-  size_t blocks = (work_items + BLOCK - 1) / BLOCK;
-  // Measured on MI355X (profiles/r1_tune_m61.txt): one pack per thread with no grid-stride wrap is the
-  // fastest geometry for every streaming kernel here; "max_blocks" caps it for experiments.
-  long cap = g_max_blocks.load();
-  if (cap <= 0) cap = 0x7fffffff;
-  if (blocks > (size_t)cap) blocks = (size_t)cap;
-  if (blocks == 0) blocks = 1;
-  return (unsigned)blocks;
-}
-
-unsigned grid_for_block(size_t work_items, int block) {
-  size_t blocks = (work_items + block - 1) / block;
-  long cap = g_max_blocks.load();
-  if (cap <= 0) cap = 0x7fffffff;
-  if (blocks > (size_t)cap) blocks = (size_t)cap;
-  if (blocks == 0) blocks = 1;
-  return (unsigned)blocks;
-}
-
+// The grids (launch_rules.hpp: grid_cap), each under its own knob.  (The launch helpers of unit_host.hpp's other parts are not
+// taken: these honour "max_blocks" / "aes_blocks".)
+// Measured on MI355X (profiles/r1_tune_m61.txt): one pack per thread with no grid-stride wrap is the
+// fastest geometry for every streaming kernel here; "max_blocks" caps it for experiments.
+unsigned grid_for(size_t work_items) { return grid_cap(work_items, BLOCK, g_max_blocks.load()); }
+unsigned grid_for_block(size_t work_items, int block) { return grid_cap(work_items, block, g_max_blocks.load()); }
 // PRG kernels carry a 32 KiB replicated AES table per block: a fixed grid of resident blocks that
 // grid-strides amortises filling it.
 unsigned grid_aes(size_t work_items) {
-  size_t blocks = (work_items + BLOCK - 1) / BLOCK;
-  long cap = g_aes_blocks.load();
-  if (cap <= 0) cap = AES_GRID_CAP;
-  if (blocks > (size_t)cap) blocks = (size_t)cap;
-  if (blocks == 0) blocks = 1;
-  return (unsigned)blocks;
+  const long cap = g_aes_blocks.load();
+  return grid_cap(work_items, BLOCK, cap > 0 ? cap : AES_GRID_CAP);
 }
-
 // The four-table AES kernels: one 1024-thread workgroup per CU (128 KiB of dynamic LDS), grid-strided.
 unsigned grid_aes4(size_t work_items) {
-  size_t blocks = (work_items + ABLOCK - 1) / ABLOCK;
-  long cap = g_aes_blocks.load();
-  if (cap <= 0) cap = AES4_GRID_CAP;
-  if (blocks > (size_t)cap) blocks = (size_t)cap;
-  if (blocks == 0) blocks = 1;
-  return (unsigned)blocks;
+  const long cap = g_aes_blocks.load();
+  return grid_cap(work_items, ABLOCK, cap > 0 ? cap : AES4_GRID_CAP);
 }
-// launch KERN (a four-table AES kernel) with its 128 KiB of dynamic LDS
-#define AES4_LAUNCH(KERN, WORK, ST, ...)                                                                            \
-  do {                                                                                                              \
-    auto kern_ = &KERN;                                                                                             \
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_), hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                                AES4_LDS_BYTES));                                                                   \
-    hipLaunchKernelGGL(kern_, dim3(grid_aes4(WORK)), dim3(ABLOCK), AES4_LDS_BYTES, ST, __VA_ARGS__);                \
-  } while (0)
 
-// ---- Mont128 modulus: a process-wide default, latched per host thread ---------------------------------------
-// scl_hip_mont128_set_prime sets the CALLING thread's modulus and the process-wide default.  A thread that has set its own
-// keeps it whatever other threads do; a thread that never set one LATCHES the default at its first use (the modulus set last
-// by any thread before that, 2^128 - 159 if none was) and keeps that value: a worker in the middle of a share-then-recover
-// sequence does not switch modulus because some other thread set a different prime.  What it must not do either is go on
-// SILENTLY: once the default has changed after a thread latched it, that thread's next Mont128 call fails with
-// SCL_ERR_BAD_ARG (its data may be residues of either modulus -- only the caller knows) until the thread says which it means:
-// scl_hip_mont128_set_prime (its own) or scl_hip_mont128_relatch (the current default).
-int mont_set(u128 p) {
-  if (!(p & 1) || p < 3) return fail(SCL_ERR_BAD_ARG, "mont128: modulus must be odd and >= 3");
-  g_mont = Mont128::make_ctx(p);
-  g_mont_own = true;
-  std::lock_guard<std::mutex> lk(g_mont_default_mu);
-  // the generation moves only when the default's VALUE does: pool workers that each set the same prime at start-up (or the
-  // built-in 2^128 - 159) change nothing for the threads that latched it
-  if (g_mont_default.p != g_mont.p) {
-    g_mont_default = g_mont;
-    ++g_mont_default_gen;
+// Launch `kern` with `lds` bytes of dynamic LDS; beyond 48 KiB a kernel needs the attribute, which is per device and cheap: set
+// on every call, so that multi-device processes are covered.  The launch status.
+template <class... P, class... A>
+hipError_t launch_lds(void (*kern)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+  if (lds) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
   }
-  g_mont_gen = g_mont_default_gen;
-  return SCL_OK;
+  hipLaunchKernelGGL(kern, grid, block, lds, st, args...);
+  return hipGetLastError();
 }
-
-void mont_latch_locked() {  // (g_mont_default_mu held)
-  if (!g_mont_default.p)
-    g_mont_default = Mont128::make_ctx((((u128)0xFFFFFFFFFFFFFFFFull) << 64) | (u128)0xFFFFFFFFFFFFFF61ull);  // 2^128 - 159
-  g_mont = g_mont_default;
-  g_mont_gen = g_mont_default_gen;
-  g_mont_own = false;
-}
-
-// SCL_OK, or the stale-latch error described above
-int mont_check() {
-  if (!g_mont.p || g_mont_own) return SCL_OK;
-  std::lock_guard<std::mutex> lk(g_mont_default_mu);
-  if (g_mont_gen == g_mont_default_gen) return SCL_OK;
-  return fail(SCL_ERR_BAD_ARG,
-              "mont128: this thread latched the process-wide default modulus at its first Mont128 call and the default has been "
-              "changed since (scl_hip_mont128_set_prime on another thread); call scl_hip_mont128_set_prime or "
-              "scl_hip_mont128_relatch on this thread to say which modulus it computes over");
-}
-
-Mont128::Ctx mont_ctx() {
-  if (g_mont.p) return g_mont;
-  std::lock_guard<std::mutex> lk(g_mont_default_mu);
-  mont_latch_locked();
-  return g_mont;
-}
-
-// (tu_config.hpp: the fields THIS translation unit instantiates kernels for)
-int not_in_this_unit() { return fail(SCL_ERR_BAD_ARG, "field family not built into this translation unit"); }
-
-template <class Fn>
-int with_field(int field, Fn&& fn) {
-  switch (field) {
-    case SCL_M61:
-      if constexpr (SCL_TU_HAS(0)) return fn(M61{}, M61::Ctx{});
-      else return not_in_this_unit();
-    case SCL_M127:
-      if constexpr (SCL_TU_HAS(1)) return fn(M127{}, M127::Ctx{});
-      else return not_in_this_unit();
-    case SCL_MONT128:
-      if constexpr (SCL_TU_HAS(2)) {
-        SCL_TRY(mont_check());
-        return fn(Mont128{}, mont_ctx());
-      } else {
-        return not_in_this_unit();
-      }
-    case SCL_GF2_128:
-      if constexpr (SCL_TU_HAS(3)) return fn(Gf128{}, Gf128::Ctx{});
-      else return not_in_this_unit();
-    case SCL_SECP256K1_SCALAR:
-      if constexpr (SCL_TU_HAS(4)) return fn(Secp256k1Scalar{}, Secp256k1Scalar::Ctx{});
-      else return not_in_this_unit();
-    case SCL_SECP256K1_FIELD:
-      if constexpr (SCL_TU_HAS(5)) return fn(Secp256k1Field{}, Secp256k1Field::Ctx{});
-      else return not_in_this_unit();
-    default: return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
-}
-
-// Rings Z2k<K> travel under the tag SCL_Z2K(K) = 0x100 + K.  Only the entry points that make sense in a ring
-// dispatch through here (element-wise, reductions, randomness, additive sharing, matmul); the Shamir and
-// Lagrange entry points stay on with_field and refuse ring tags, as division by node differences would.
-inline bool is_ring(int field) { return field > 0x100 && field <= 0x100 + 128; }
-
-template <class Fn>
-int with_ring_or_field(int field, Fn&& fn) {
-  if (is_ring(field)) {
-    const int K = field - 0x100;
-    if constexpr (SCL_TU_HAS(6)) {
-      if (K <= 64) return fn(Z2k64{}, Z2k64::make_ctx(K));
-      return fn(Z2k128{}, Z2k128::make_ctx(K));
-    } else {
-      return not_in_this_unit();
-    }
-  }
-  return with_field(field, fn);
-}
-
-// ---- per-thread device scratch (only used by calls that synchronise before returning) -------------
-
-int scratch(size_t bytes, void** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (g_scratch.dev && (g_scratch.device != dev || g_scratch.bytes < bytes)) {
-    (void)hipFree(g_scratch.dev);
-    g_scratch = Scratch{};
-  }
-  if (!g_scratch.dev) {
-    size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    HIP_TRY(hipMalloc(&g_scratch.dev, want));
-    g_scratch.device = dev;
-    g_scratch.bytes = want;
-  }
-  *out = g_scratch.dev;
-  return SCL_OK;
-}
-
-// ---- per-thread device temporary for asynchronous calls ---------------------------------------------------
-// A kernel-written temporary that outlives the call (the call returns before its kernels ran).  One buffer per
-// host thread, kept and grown; an event recorded after the last use makes the next user -- possibly on another
-// stream -- wait for it.  (hipMallocAsync / hipFreeAsync on the null stream proved unreliable under the ROCm 7.2
-// runtime: a queue allocated that way lost writes between two kernels of one call.)
-
-int temp_acquire(size_t bytes, hipStream_t st, void** out, int which = 0) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  TempArena& a = g_temps[which];
-  if (a.dev && (a.device != dev || a.bytes < bytes)) {
-    if (a.pending) HIP_TRY(hipEventSynchronize(a.done));
-    (void)hipFree(a.dev);
-    (void)hipEventDestroy(a.done);
-    a = TempArena{};
-  }
-  if (!a.dev) {
-    HIP_TRY(hipMalloc(&a.dev, bytes < (1u << 20) ? (1u << 20) : bytes));
-    HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-    a.device = dev;
-    a.bytes = bytes < (1u << 20) ? (1u << 20) : bytes;
-  }
-  if (a.pending) HIP_TRY(hipStreamWaitEvent(st, a.done, 0));
-  *out = a.dev;
-  return SCL_OK;
-}
-
-// An arena is kept for the thread's next call up to TEMP_RETAIN_BYTES; a larger one (the digit planes of a matrix product
-// with both factors beyond ~4096 x 4096, or with K beyond 2^21: the planes grow with K, 512 bytes per 32-row tile and inner
-// column) goes back when the call that grew it ends -- hipFree waits for that call's kernels, which run for milliseconds
-// at such sizes; the retained arenas are what scl_hip_thread_cleanup frees.
-constexpr size_t TEMP_RETAIN_BYTES = (size_t)1 << 30;
-
-int temp_release(hipStream_t st, int which = 0) {
-  TempArena& a = g_temps[which];
-  if (a.dev && a.bytes > TEMP_RETAIN_BYTES) {
-    HIP_TRY(hipStreamSynchronize(st));
-    (void)hipFree(a.dev);
-    (void)hipEventDestroy(a.done);
-    a = TempArena{};
-    return SCL_OK;
-  }
-  HIP_TRY(hipEventRecord(a.done, st));
-  a.pending = true;
-  return SCL_OK;
+// a four-table AES kernel with its 128 KiB of tables, grid-strided over `work` items
+template <class... P, class... A>
+hipError_t launch_aes4(void (*kern)(P...), size_t work, hipStream_t st, const A&... args) {
+  return launch_lds(kern, dim3(grid_aes4(work)), dim3(ABLOCK), AES4_LDS_BYTES, st, args...);
 }
 
 // ---- host tables ---------------------------------------------------------------------------------
@@ -554,7 +273,6 @@ int alpha_table(const typename F::Ctx& ctx, const u64* alphas_host, size_t n, Bi
   return SCL_OK;
 }
 
-
 #define LAUNCH_CHECK() HIP_TRY(hipGetLastError())
 
 // ---- MFMA share path (Mersenne61): limb planes of the Vandermonde matrix, cached per device ----------
@@ -563,124 +281,102 @@ int alpha_table(const typename F::Ctx& ctx, const u64* alphas_host, size_t n, Bi
 // while 16 entries are cached -- is therefore freed only when the last pin drops, i.e. after the launch; hipFree then waits
 // for the kernels already enqueued, the pinning one included.
 using DevPin = std::shared_ptr<void>;
-inline DevPin make_dev_pin(void* dev) {
-  return DevPin(dev, [](void* p) { (void)hipFree(p); });
-}
-struct MfmaTable {
-  int device, n, t, KS, MT;
-  std::vector<u64> alphas;
-  DevPin dev;
-};
-std::mutex g_mfma_mu;
-std::vector<MfmaTable> g_mfma_tables;  // immutable once built; most recently used last, at most TABLE_CACHE_CAP entries
 constexpr size_t TABLE_CACHE_CAP = 16;
 
-// Keeps a table cache bounded: a hit moves its entry to the back, a miss past the cap drops the cache's reference to the
-// front (least recently used) entry; the table itself goes when no caller pins it any more (DevPin above).
-template <class Entry>
-void cache_touch(std::vector<Entry>& cache, size_t hit) {
-  if (hit + 1 != cache.size()) std::rotate(cache.begin() + hit, cache.begin() + hit + 1, cache.end());
-}
-template <class Entry>
-void cache_make_room(std::vector<Entry>& cache) {
-  while (cache.size() >= TABLE_CACHE_CAP) cache.erase(cache.begin());
-}
+// A bounded cache of device tables, per device and key: a hit moves its entry to the back, a miss past the cap drops the
+// cache's reference to the front (least recently used) entry; the table itself goes when no caller pins it any more.
+template <class Key>
+class DeviceTableCache {
+  struct Entry {
+    int device;
+    Key key;
+    DevPin dev;
+  };
+  std::mutex mu_;
+  std::vector<Entry> entries_;  // immutable once built; most recently used last, at most TABLE_CACHE_CAP entries
+
+ public:
+  // the table under `key` on the current device; a miss builds it: fill(host) writes its `bytes` bytes (zeroed)
+  template <class Fill>
+  int get(const Key& key, size_t bytes, Fill&& fill, DevPin* pin, const void** ptr) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(mu_);
+    for (size_t k = 0; k < entries_.size(); ++k) {
+      if (entries_[k].device != dev || !(entries_[k].key == key)) continue;
+      *pin = entries_[k].dev;
+      *ptr = pin->get();
+      if (k + 1 != entries_.size()) std::rotate(entries_.begin() + k, entries_.begin() + k + 1, entries_.end());
+      return SCL_OK;
+    }
+    while (entries_.size() >= TABLE_CACHE_CAP) entries_.erase(entries_.begin());
+    std::vector<unsigned char> host(bytes, 0);
+    fill(host.data());
+    void* raw = nullptr;
+    HIP_TRY(hipMalloc(&raw, bytes));
+    Entry e{dev, key, DevPin(raw, [](void* p) { (void)hipFree(p); })};
+    HIP_TRY(hipMemcpy(raw, host.data(), bytes, hipMemcpyHostToDevice));
+    entries_.push_back(e);
+    *pin = e.dev;
+    *ptr = raw;
+    return SCL_OK;
+  }
+};
+DeviceTableCache<std::vector<u64>> g_mfma_tables, g_vdm_tables;
 
 template <class FieldG>
 int mfma_table(const BigTable<M61>& al, size_t n, size_t t, int KS, int MT, DevPin* pin, const unsigned char** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(g_mfma_mu);
-  for (size_t k = 0; k < g_mfma_tables.size(); ++k) {
-    const MfmaTable& e = g_mfma_tables[k];
-    if (e.device == dev && e.n == (int)n && e.t == (int)t && e.KS == KS && e.MT == MT &&
-        std::equal(e.alphas.begin(), e.alphas.end(), al.v)) {
-      *pin = e.dev;
-      *out = static_cast<const unsigned char*>(e.dev.get());
-      cache_touch(g_mfma_tables, k);
-      return SCL_OK;
+  std::vector<u64> key{(u64)n, (u64)t, (u64)KS, (u64)MT};
+  key.insert(key.end(), al.v, al.v + n);
+  const void* tab = nullptr;
+  SCL_TRY(g_mfma_tables.get(key, mf_a_bytes(KS, MT), [&](unsigned char* host) {
+    const int ROWB = mf_rowb(KS);
+    const M61::Ctx ctx{};
+    for (size_t i = 0; i < n; ++i) {
+      u64 v = 1;  // alpha_i^k, Matrix::vandermonde (matrix.h:444-460)
+      for (size_t k = 0; k <= t; ++k) {
+        if (k) v = M61::mul(ctx, v, al.v[i]);
+        const u64 digits = mf_recode(v);  // 8 signed base-256 digits, one per byte
+        for (int l = 0; l < MF_LIMBS; ++l)
+          host[((size_t)(l * MT + (int)(i / 32)) * 32 + (i % 32)) * ROWB + k] = (unsigned char)(digits >> (8 * l));
+      }
     }
-  }
-  cache_make_room(g_mfma_tables);
-  const int ROWB = mf_rowb(KS);
-  std::vector<unsigned char> host(mf_a_bytes(KS, MT), 0);
-  const M61::Ctx ctx{};
-  for (size_t i = 0; i < n; ++i) {
-    u64 v = 1;  // alpha_i^k, Matrix::vandermonde (matrix.h:444-460)
-    for (size_t k = 0; k <= t; ++k) {
-      if (k) v = M61::mul(ctx, v, al.v[i]);
-      const u64 digits = mf_recode(v);  // 8 signed base-256 digits, one per byte
-      for (int l = 0; l < MF_LIMBS; ++l)
-        host[((size_t)(l * MT + (int)(i / 32)) * 32 + (i % 32)) * ROWB + k] = (unsigned char)(digits >> (8 * l));
-    }
-  }
-  void* raw = nullptr;
-  HIP_TRY(hipMalloc(&raw, host.size()));
-  MfmaTable e{dev, (int)n, (int)t, KS, MT, std::vector<u64>(al.v, al.v + n), make_dev_pin(raw)};
-  HIP_TRY(hipMemcpy(raw, host.data(), host.size(), hipMemcpyHostToDevice));
-  g_mfma_tables.push_back(e);
-  *pin = e.dev;
-  *out = static_cast<const unsigned char*>(raw);
+  }, pin, &tab));
+  *out = static_cast<const unsigned char*>(tab);
   return SCL_OK;
 }
 
 // The kernel by shape (profiles/r5_probe_auto_choices.txt): four row tiles (65..128 parties) go to the pipelined kernels,
 // k_share_mfma_m61_p16 with two k-steps and k_share_mfma_m61_pipe<1> with one; fewer row tiles to k_share_mfma_m61.
-template <int KS, int MT>
+// ACC: Matrix::multiply's k-chunks after the first, the same kernels with their stores adding to what the rows hold (the
+// pipelined one-k-step kernel has no such form: k_share_mfma_m61 takes its shape then).
+template <int KS, int MT, bool ACC>
 int launch_share_mfma(u64* shares, size_t stride, const u64* secrets, const u64* coeffs, size_t cstride,
-                      const unsigned char* tab, int t, int n, size_t N, hipStream_t st, bool accumulate = false) {
-  if (accumulate) {
-    // Matrix::multiply's k-chunks after the first: the same kernels with their stores adding to what the rows hold
-    if constexpr (MT == 4 && KS == 2) {
-      auto kern = &k_share_mfma_m61_p16<M61, true>;
-      const size_t shmem = 2 * mf_b_bytes(KS, MT, 1);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-      const size_t nblocks = (N + 31) / 32;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < 256 ? nblocks : 256)), dim3(512), shmem, st, shares, stride, secrets, coeffs,
-                         cstride, tab, t, n, N);
-    } else {
-      auto kern = &k_share_mfma_m61<KS, MT, true>;
-      const size_t shmem = mf_a_bytes(KS, MT) + mf_b_bytes(KS, MT);
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-      const size_t cols = (size_t)2 * (4 / MT) * 32, nblocks = (N + cols - 1) / cols;
-      hipLaunchKernelGGL(kern, dim3((unsigned)(nblocks < 256 ? nblocks : 256)), dim3(512), shmem, st, shares, stride, secrets, coeffs,
-                         cstride, tab, t, n, N);
-    }
-    HIP_TRY(hipGetLastError());
-    return SCL_OK;
-  }
-  if constexpr (MT == 4 && KS == 2) {
-    // k_share_mfma_m61_p16: one 8-wave workgroup per CU, 32 secrets per trip, two LDS images of the recoded block
-    const size_t shmem = 2 * mf_b_bytes(KS, MT, 1);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61_p16<>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    const size_t nblocks = (N + 31) / 32;
-    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
-    hipLaunchKernelGGL(k_share_mfma_m61_p16<>, dim3(grid), dim3(512), shmem, st, shares, stride, secrets, coeffs, cstride, tab,
-                       t, n, N);
-  } else if constexpr (MT == 4) {
-    // k_share_mfma_m61_pipe: one 4-wave workgroup per CU, 32 secrets per trip
-    const size_t shmem = mf_b_bytes(KS, MT, 1);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61_pipe<KS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    const size_t nblocks = (N + 31) / 32;
-    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
-    hipLaunchKernelGGL((k_share_mfma_m61_pipe<KS>), dim3(grid), dim3(256), shmem, st, shares, stride, secrets, coeffs,
-                       cstride, tab, t, n, N);
-  } else {
-    // k_share_mfma_m61: one 8-wave workgroup per CU, grid-strided; V's digit planes and the recoded block in LDS
-    const size_t shmem = mf_a_bytes(KS, MT) + mf_b_bytes(KS, MT);
-    // per device and cheap: set on every call so that multi-device processes are covered
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_share_mfma_m61<KS, MT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    const size_t cols = (size_t)2 * (4 / MT) * 32;
+                      const unsigned char* tab, int t, int n, size_t N, hipStream_t st) {
+  // workgroups of `block` threads taking `cols` secrets per trip, at most one per CU
+  auto launch = [&](auto kern, size_t cols, unsigned block, size_t shmem) -> int {
     const size_t nblocks = (N + cols - 1) / cols;
-    const unsigned grid = (unsigned)(nblocks < 256 ? nblocks : 256);
-    hipLaunchKernelGGL((k_share_mfma_m61<KS, MT>), dim3(grid), dim3(512), shmem, st, shares, stride, secrets, coeffs,
-                       cstride, tab, t, n, N);
-  }
-  HIP_TRY(hipGetLastError());
-  return SCL_OK;
+    HIP_TRY(launch_lds(kern, dim3((unsigned)(nblocks < 256 ? nblocks : 256)), dim3(block), shmem, st, shares, stride, secrets,
+                       coeffs, cstride, tab, t, n, N));
+    return SCL_OK;
+  };
+  if constexpr (MT == 4 && KS == 2)  // one 8-wave workgroup per CU, 32 secrets per trip, two LDS images of the recoded block
+    return launch(&k_share_mfma_m61_p16<M61, ACC>, 32, 512, 2 * mf_b_bytes(KS, MT, 1));
+  else if constexpr (MT == 4 && !ACC)  // one 4-wave workgroup per CU, 32 secrets per trip
+    return launch(&k_share_mfma_m61_pipe<KS>, 32, 256, mf_b_bytes(KS, MT, 1));
+  else  // one 8-wave workgroup per CU, grid-strided; V's digit planes and the recoded block in LDS
+    return launch(&k_share_mfma_m61<KS, MT, ACC>, (size_t)2 * (4 / MT) * 32, 512, mf_a_bytes(KS, MT) + mf_b_bytes(KS, MT));
+}
+
+// fn(KS, MT as integral constants) for the shape's pair, one of the five the kernels are built for; `unsupported` names
+// the caller in the failure for any other
+template <class Fn>
+int with_mfma_shape(MfmaShape s, const char* unsupported, Fn&& fn) {
+  int rc = SCL_OK;
+  const bool found = dispatch_of<11, 12, 14, 22, 24>(s.KS * 10 + s.MT, [&](auto P) {
+    rc = fn(std::integral_constant<int, decltype(P)::value / 10>{}, std::integral_constant<int, decltype(P)::value % 10>{});
+  });
+  return found ? rc : fail(SCL_ERR_BAD_ARG, unsupported);
 }
 
 // C[M x N] = A[M x K] * B[K x N] over Mersenne61 on the matrix cores: A's digit planes are built on the
@@ -700,9 +396,10 @@ int matmul_mfma_impl(u64* C, size_t ldc, const u64* A, size_t lda, const u64* B,
   void* tab = nullptr;
   SCL_TRY(temp_acquire(mf_a_bytes(KS, MT), st, &tab));
   int rc = mfma_planes_of<KS, MT>(tab, A, lda, M, K, st);
+  const unsigned char* planes = static_cast<const unsigned char*>(tab);
   if (rc == SCL_OK)
-    rc = launch_share_mfma<KS, MT>(C, ldc, B, B + ldb, ldb, static_cast<const unsigned char*>(tab), (int)K - 1, (int)M, N,
-                                   st, accumulate);
+    rc = accumulate ? launch_share_mfma<KS, MT, true>(C, ldc, B, B + ldb, ldb, planes, (int)K - 1, (int)M, N, st)
+                    : launch_share_mfma<KS, MT, false>(C, ldc, B, B + ldb, ldb, planes, (int)K - 1, (int)M, N, st);
   (void)temp_release(st);
   return rc;
 }
@@ -710,14 +407,9 @@ int matmul_mfma_impl(u64* C, size_t ldc, const u64* A, size_t lda, const u64* B,
 template <class FieldG>
 int matmul_mfma(u64* C, size_t ldc, const u64* A, size_t lda, const u64* B, size_t ldb, size_t M, size_t K, size_t N,
                 hipStream_t st, bool accumulate = false) {
-  const int KS = K <= 32 ? 1 : 2;
-  // (one row tile with two k-steps would need 160 KiB for the staged right factor: such shapes take two row tiles)
-  const int MT = (M <= 32 && KS == 1) ? 1 : M <= 64 ? 2 : 4;
-#define MM_CASE(ks, mt) \
-  if (KS == ks && MT == mt) return matmul_mfma_impl<ks, mt>(C, ldc, A, lda, B, ldb, M, K, N, st, accumulate);
-  MM_CASE(1, 1) MM_CASE(1, 2) MM_CASE(1, 4) MM_CASE(2, 2) MM_CASE(2, 4)
-#undef MM_CASE
-  return fail(SCL_ERR_BAD_ARG, "matmul_mfma: unsupported shape");
+  return with_mfma_shape(mfma_shape(M, K), "matmul_mfma: unsupported shape", [&](auto KS, auto MT) {
+    return matmul_mfma_impl<decltype(KS)::value, decltype(MT)::value>(C, ldc, A, lda, B, ldb, M, K, N, st, accumulate);
+  });
 }
 
 // Any M and K on the matrix cores: row blocks of at most 128 rows of A, column chunks of at most 64 (the kernel's K).  The first
@@ -812,7 +504,7 @@ int detect_mfma_impl(u64* out, unsigned char* status, const u64* shares, size_t 
     SCL_TRY((mfma_planes_of<KS, MT>(base, L_dev, d1, rows, d1, st)));
     for (size_t s0 = 0; s0 < N; s0 += slab) {
       const size_t ns = std::min(slab, N - s0);
-      SCL_TRY((launch_share_mfma<KS, MT>(Y, ldy, shares + s0, shares + stride + s0, stride, base, (int)d1 - 1, (int)rows, ns, st)));
+      SCL_TRY((launch_share_mfma<KS, MT, false>(Y, ldy, shares + s0, shares + stride + s0, stride, base, (int)d1 - 1, (int)rows, ns, st)));
       hipLaunchKernelGGL((k_detect_compare<M61>), dim3(grid_for(ns)), dim3(BLOCK), 0, st, out + s0, status + s0, Y, ldy,
                          shares + d1 * stride + s0, stride, (int)rows - 1, ns, cnt);
       HIP_TRY(hipGetLastError());
@@ -827,40 +519,26 @@ int detect_mfma_impl(u64* out, unsigned char* status, const u64* shares, size_t 
 template <class FieldG>
 int detect_mfma(u64* out, unsigned char* status, const u64* shares, size_t stride, const std::vector<u64>& L, size_t rows,
                 size_t d1, size_t N, unsigned long long* cnt, hipStream_t st) {
-  const int KS = d1 <= 32 ? 1 : 2;
-  const int MT = (rows <= 32 && KS == 1) ? 1 : rows <= 64 ? 2 : 4;
-#define DM_CASE(ks, mt) \
-  if (KS == ks && MT == mt) return detect_mfma_impl<ks, mt>(out, status, shares, stride, L, rows, d1, N, cnt, st);
-  DM_CASE(1, 1) DM_CASE(1, 2) DM_CASE(1, 4) DM_CASE(2, 2) DM_CASE(2, 4)
-#undef DM_CASE
-  return fail(SCL_ERR_BAD_ARG, "detect_mfma: unsupported shape");
+  return with_mfma_shape(mfma_shape(rows, d1), "detect_mfma: unsupported shape", [&](auto KS, auto MT) {
+    return detect_mfma_impl<decltype(KS)::value, decltype(MT)::value>(out, status, shares, stride, L, rows, d1, N, cnt, st);
+  });
 }
 
 template <class FieldG>
 int share_mfma(const BigTable<M61>& al, u64* shares, size_t stride, const u64* secrets, const u64* coeffs,
                size_t cstride, size_t N, size_t t, size_t n, hipStream_t st) {
-  const int KS = t + 1 <= 32 ? 1 : 2;
-  const int MT = (n <= 32 && KS == 1) ? 1 : n <= 64 ? 2 : 4;  // (as matmul_mfma: no one-row-tile form with two k-steps)
+  const MfmaShape shape = mfma_shape(n, t + 1);
   const unsigned char* tab = nullptr;
   DevPin pin;  // held until the launch below is enqueued
-  SCL_TRY(mfma_table<FieldG>(al, n, t, KS, MT, &pin, &tab));
-#define MF_CASE(ks, mt) \
-  if (KS == ks && MT == mt) return launch_share_mfma<ks, mt>(shares, stride, secrets, coeffs, cstride, tab, (int)t, (int)n, N, st);
-  MF_CASE(1, 1) MF_CASE(1, 2) MF_CASE(1, 4) MF_CASE(2, 2) MF_CASE(2, 4)
-#undef MF_CASE
-  return fail(SCL_ERR_BAD_ARG, "share_mfma: unsupported shape");
+  SCL_TRY(mfma_table<FieldG>(al, n, t, shape.KS, shape.MT, &pin, &tab));
+  return with_mfma_shape(shape, "share_mfma: unsupported shape", [&](auto KS, auto MT) {
+    return launch_share_mfma<decltype(KS)::value, decltype(MT)::value, false>(shares, stride, secrets, coeffs, cstride, tab, (int)t,
+                                                                              (int)n, N, st);
+  });
 }
 
 // Device-resident Vandermonde power tables of the Montgomery-field share kernels (k_share_vdm): row i holds
 // table_scale(alpha_i^k), k = 1..t.  Cached per (device, field parameters, nodes, t) like the MFMA tables.
-struct VdmTable {
-  int device, tag, n, t;
-  std::vector<u64> key;  // raw_coeffs flag, field parameters (Mont128: the prime), then the nodes
-  DevPin dev;
-};
-std::mutex g_vdm_mu;
-std::vector<VdmTable> g_vdm_tables;  // immutable once built; bounded like g_mfma_tables
-
 template <class F>
 bool vdm_eligible(size_t n, size_t t) {
   return (F::TAG == 2 || F::LIMBS == 4) && t >= 1 && t <= 16 && n * t * F::LIMBS <= (size_t)VdmLds::WORDS;
@@ -868,9 +546,8 @@ bool vdm_eligible(size_t n, size_t t) {
 
 template <class F>
 int vdm_table(const typename F::Ctx& ctx, const BigTable<F>& al, size_t n, size_t t, bool raw_coeffs, DevPin* pin, const u64** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  std::vector<u64> key{raw_coeffs ? 1u : 0u};
+  // the field, the shape, the raw_coeffs flag, the field parameters (Mont128: the prime), then the nodes
+  std::vector<u64> key{(u64)F::TAG, (u64)n, (u64)t, raw_coeffs ? 1u : 0u};
   if constexpr (F::TAG == 2) {
     key.push_back((u64)ctx.p);
     key.push_back((u64)(ctx.p >> 64));
@@ -880,34 +557,20 @@ int vdm_table(const typename F::Ctx& ctx, const BigTable<F>& al, size_t n, size_
     F::st(w, al.v[i]);
     key.insert(key.end(), w, w + F::LIMBS);
   }
-  std::lock_guard<std::mutex> lk(g_vdm_mu);
-  for (size_t k = 0; k < g_vdm_tables.size(); ++k) {
-    const VdmTable& e = g_vdm_tables[k];
-    if (e.device == dev && e.tag == (int)F::TAG && e.n == (int)n && e.t == (int)t && e.key == key) {
-      *pin = e.dev;
-      *out = static_cast<const u64*>(e.dev.get());
-      cache_touch(g_vdm_tables, k);
-      return SCL_OK;
+  const void* tab = nullptr;
+  SCL_TRY(g_vdm_tables.get(key, n * t * F::LIMBS * sizeof(u64), [&](unsigned char* bytes) {
+    u64* host = reinterpret_cast<u64*>(bytes);
+    for (size_t i = 0; i < n; ++i) {
+      typename F::E v = al.v[i];  // alpha_i^k, Matrix::vandermonde (matrix.h:444-460)
+      for (size_t k = 1; k <= t; ++k) {
+        // raw_coeffs: the kernel multiplies by plain integers x, not residues xR, so the row carries the R
+        const typename F::E entry = raw_coeffs ? F::to_mont(ctx, v) : v;
+        F::st(host + (i * t + (k - 1)) * F::LIMBS, F::table_scale(ctx, entry));
+        v = F::mul(ctx, v, al.v[i]);
+      }
     }
-  }
-  cache_make_room(g_vdm_tables);
-  std::vector<u64> host(n * t * F::LIMBS);
-  for (size_t i = 0; i < n; ++i) {
-    typename F::E v = al.v[i];  // alpha_i^k, Matrix::vandermonde (matrix.h:444-460)
-    for (size_t k = 1; k <= t; ++k) {
-      // raw_coeffs: the kernel multiplies by plain integers x, not residues xR, so the row carries the R
-      const typename F::E entry = raw_coeffs ? F::to_mont(ctx, v) : v;
-      F::st(host.data() + (i * t + (k - 1)) * F::LIMBS, F::table_scale(ctx, entry));
-      v = F::mul(ctx, v, al.v[i]);
-    }
-  }
-  void* raw = nullptr;
-  HIP_TRY(hipMalloc(&raw, host.size() * sizeof(u64)));
-  VdmTable e{dev, (int)F::TAG, (int)n, (int)t, key, make_dev_pin(raw)};
-  HIP_TRY(hipMemcpy(raw, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice));
-  g_vdm_tables.push_back(e);
-  *pin = e.dev;
-  *out = static_cast<const u64*>(raw);
+  }, pin, &tab));
+  *out = static_cast<const u64*>(tab);
   return SCL_OK;
 }
 
@@ -955,43 +618,36 @@ bool small_lambda(const typename F::Ctx& ctx, const u64* lambda_host, size_t m, 
   }
 }
 
-template <class F, int M>
-struct RecoverSmall {
-  static int run(const typename F::Ctx& ctx, u64* out, const u64* shares, size_t stride, const SmallLam& lam, int m, size_t n,
-                 hipStream_t st) {
-    if (m == M) {
-      // single-wave workgroups under the residency cap of the (m <= 16) stream kernels (kernels.hpp, "Launch geometry")
-      const long sw = g_stream_waves.load();
-      const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 4 ? 10 : 12) : sw, 64, 0);  // (profiles/r5_probe_f3_waves.txt)
-      const size_t lanes = F::LIMBS == 4 ? 2 * n : n;  // 32-byte elements: a pair of lanes per secret
-      hipLaunchKernelGGL((k_recover_small<F, M>), dim3(grid_for_block(lanes, 64)), dim3(64), pad, st, ctx, out, shares, stride,
-                         lam, n);
-      HIP_TRY(hipGetLastError());
-      return SCL_OK;
-    }
-    if constexpr (M > 1) return RecoverSmall<F, M - 1>::run(ctx, out, shares, stride, lam, m, n, st);
-    return fail(SCL_ERR_BAD_ARG, "recover: internal");
-  }
-};
+// k_recover_small<F, m>, m = 1..FIXED_M_MAX
+template <class F>
+int recover_small(const typename F::Ctx& ctx, u64* out, const u64* shares, size_t stride, const SmallLam& lam, int m, size_t n,
+                  hipStream_t st) {
+  // single-wave workgroups under the residency cap of the (m <= 16) stream kernels (kernels.hpp, "Launch geometry")
+  const long sw = g_stream_waves.load();
+  const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 4 ? 10 : 12) : sw, 64, 0);  // (profiles/r5_probe_f3_waves.txt)
+  const size_t lanes = F::LIMBS == 4 ? 2 * n : n;  // 32-byte elements: a pair of lanes per secret
+  const bool found = dispatch_int<1, FIXED_M_MAX>(m, [&](auto M) {
+    hipLaunchKernelGGL((k_recover_small<F, decltype(M)::value>), dim3(grid_for_block(lanes, 64)), dim3(64), pad, st, ctx, out, shares,
+                       stride, lam, n);
+  });
+  if (!found) return fail(SCL_ERR_BAD_ARG, "recover: internal");
+  HIP_TRY(hipGetLastError());
+  return SCL_OK;
+}
 
-template <class F, int M>
-struct RecoverFixed {
-  template <int VEC>
-  static int run(const typename F::Ctx& ctx, u64* out, const u64* shares, size_t stride, const Table<F>& lam, int m,
-                 size_t npacks, hipStream_t st) {
-    if (m == M) {
-      // single-wave workgroups under the residency cap (kernels.hpp, "Launch geometry")
-      const long sw = g_stream_waves.load();
-      const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 1 ? 10 : 12) : sw, 64, 0);
-      hipLaunchKernelGGL((k_recover_fixed<F, VEC, M>), dim3(grid_for_block(npacks, 64)), dim3(64), pad, st, ctx, out, shares,
-                         stride, lam, npacks);
-      return SCL_OK;
-    }
-    if constexpr (M > 1) return RecoverFixed<F, M - 1>::template run<VEC>(ctx, out, shares, stride, lam, m, npacks, st);
-    return fail(SCL_ERR_BAD_ARG, "recover: m out of range");
-  }
-};
-
+// k_recover_fixed<F, VEC, m>, m = 1..FIXED_M_MAX (the caller checks the launch)
+template <class F, int VEC>
+int recover_fixed(const typename F::Ctx& ctx, u64* out, const u64* shares, size_t stride, const Table<F>& lam, int m, size_t npacks,
+                  hipStream_t st) {
+  // single-wave workgroups under the residency cap (kernels.hpp, "Launch geometry")
+  const long sw = g_stream_waves.load();
+  const size_t pad = residency_pad(sw < 0 ? (F::LIMBS == 1 ? 10 : 12) : sw, 64, 0);
+  const bool found = dispatch_int<1, FIXED_M_MAX>(m, [&](auto M) {
+    hipLaunchKernelGGL((k_recover_fixed<F, VEC, decltype(M)::value>), dim3(grid_for_block(npacks, 64)), dim3(64), pad, st, ctx, out,
+                       shares, stride, lam, npacks);
+  });
+  return found ? SCL_OK : fail(SCL_ERR_BAD_ARG, "recover: m out of range");
+}
 
 // the n nodes first_party+1 .. (default: FF(int) images, vector.h:490-505) or the caller's, as host limbs
 static int nodes_to_host(int field, const uint64_t* alphas_host, size_t n, size_t first_party, u64* out) {
@@ -1068,10 +724,8 @@ int launch_inv_rolled(const typename F::Ctx& ctx, u64* dst, const u64* a, const 
   using ARITH = std::conditional_t<F::TAG == 3, GfLdsArith<BLK, 3>, FieldArith<F>>;
   auto kern = &k_ew_inv_rolled<F, ARITH, DIV, L, BLK>;
   const size_t lds = (size_t)BLK * ARITH::LDS_PER_LANE;
-  if (lds) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const size_t tiles = (n + (size_t)BLK * L - 1) / ((size_t)BLK * L);
-  hipLaunchKernelGGL(kern, dim3(grid_for_block(tiles, 1)), dim3(BLK), lds, st, ctx, dst, a, b, n, flag);
-  LAUNCH_CHECK();
+  HIP_TRY(launch_lds(kern, dim3(grid_for_block(tiles, 1)), dim3(BLK), lds, st, ctx, dst, a, b, n, flag));
   return SCL_OK;
 }
 
@@ -1097,10 +751,9 @@ int launch_inv_blocked(const typename F::Ctx& ctx, u64* dst, const u64* a, const
 }
 template <class F, bool DIV, int L2>
 int launch_inv_blocked_by_length(const typename F::Ctx& ctx, u64* dst, const u64* a, const u64* b, size_t n, int L, unsigned* flag, hipStream_t st) {
-  if (L == 256) return launch_inv_blocked<F, DIV, 256, L2>(ctx, dst, a, b, n, flag, st);
-  if (L == 128) return launch_inv_blocked<F, DIV, 128, L2>(ctx, dst, a, b, n, flag, st);
-  if (L == 64) return launch_inv_blocked<F, DIV, 64, L2>(ctx, dst, a, b, n, flag, st);
-  return launch_inv_blocked<F, DIV, 32, L2>(ctx, dst, a, b, n, flag, st);
+  int rc = SCL_OK;  // (L is 32, 64, 128 or 256 here: ew_inverse_rolled)
+  dispatch_of<32, 64, 128, 256>(L, [&](auto LL) { rc = launch_inv_blocked<F, DIV, decltype(LL)::value, L2>(ctx, dst, a, b, n, flag, st); });
+  return rc;
 }
 
 template <class F, bool DIV>
@@ -1125,11 +778,9 @@ int ew_inverse_rolled(const typename F::Ctx& ctx, u64* dst, const u64* a, const 
     if (L >= 32 && two >= 8) return launch_inv_blocked_by_length<F, DIV, 8>(ctx, dst, a, b, n, L, flag, st);
     if (L >= 32 && two >= 1) return launch_inv_blocked_by_length<F, DIV, 4>(ctx, dst, a, b, n, L, flag, st);
   }
-  if (L >= 128) return launch_inv_rolled<F, DIV, 128>(ctx, dst, a, b, n, flag, st);   // (256: the two-level form only)
-  if (L == 64) return launch_inv_rolled<F, DIV, 64>(ctx, dst, a, b, n, flag, st);
-  if (L == 32) return launch_inv_rolled<F, DIV, 32>(ctx, dst, a, b, n, flag, st);
-  if (L == 16) return launch_inv_rolled<F, DIV, 16>(ctx, dst, a, b, n, flag, st);
-  return launch_inv_rolled<F, DIV, 8>(ctx, dst, a, b, n, flag, st);
+  int rc = SCL_OK;  // (256: the two-level form only)
+  dispatch_of<8, 16, 32, 64, 128>(L >= 128 ? 128 : L, [&](auto LL) { rc = launch_inv_rolled<F, DIV, decltype(LL)::value>(ctx, dst, a, b, n, flag, st); });
+  return rc;
 }
 
 template <class F>
@@ -1424,14 +1075,9 @@ static int ew_impl(int field, int op, uint64_t* dst, const uint64_t* a, const ui
         const u64* pa = a + first * F::LIMBS;
         const u64* pb = binary ? b + first * F::LIMBS : nullptr;
         const dim3 g(grid_for(npacks)), blk(BLOCK);
-#define EW_CASE(OP)                                                                                             \
-  case OP:                                                                                                      \
-    hipLaunchKernelGGL((k_ew<F, OP, VEC>), g, blk, 0, S(stream), ctx, d, pa, pb, npacks, flag);                 \
-    break;
-        switch (op) {
-          EW_CASE(0) EW_CASE(1) EW_CASE(2) EW_CASE(3) EW_CASE(4) EW_CASE(5)
-        }
-#undef EW_CASE
+        dispatch_int<0, 5>(op, [&](auto OP) {  // (op was checked above)
+          hipLaunchKernelGGL((k_ew<F, decltype(OP)::value, VEC>), g, blk, 0, S(stream), ctx, d, pa, pb, npacks, flag);
+        });
         LAUNCH_CHECK();
         return SCL_OK;
       });
@@ -1516,11 +1162,9 @@ static int reduce_impl(int field, uint64_t* out_host, const uint64_t* a, const u
       if (is_dot && g_inv_batch.load() >= 0) {  // GF(2^128): the products on per-lane window tables in LDS (k_dot_gf128)
         constexpr int BLK = 256;
         auto kern = &k_dot_gf128<BLK, 3>;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, BLK * 128));
         size_t g = (n + BLK - 1) / BLK;
         if (g > 4096) g = 4096;  // resident workgroups that stride: each partial costs a host-side add
-        hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(BLK), BLK * 128, S(stream), part1, a, b, n);
-        LAUNCH_CHECK();
+        HIP_TRY(launch_lds(kern, dim3((unsigned)g), dim3(BLK), BLK * 128, S(stream), part1, a, b, n));
         used1 = (unsigned)g;
         staged = true;
       }
@@ -1611,8 +1255,7 @@ int scl_hip_prg_blocks(unsigned char* dst, size_t nblocks, const unsigned char* 
   AesKey key;
   make_aes_key(seed, seed_len, key);
   aes_key_range(key, (u64)counter0, (u64)nblocks);
-  AES4_LAUNCH(k_prg_blocks<>, (nblocks + 3) / 4, S(stream), reinterpret_cast<u64*>(dst), key, (u64)counter0, nblocks);
-  LAUNCH_CHECK();
+  HIP_TRY(launch_aes4(&k_prg_blocks<>, (nblocks + 3) / 4, S(stream), reinterpret_cast<u64*>(dst), key, (u64)counter0, nblocks));
   return SCL_OK;
 }
 #endif  // SCL_TU_COMMON
@@ -1677,11 +1320,9 @@ int scl_hip_vector_random(int field, uint64_t* dst, size_t n, const unsigned cha
     make_aes_key(seed, seed_len, key);
     aes_key_range(key, (u64)counter0, ((u64)n * F::LIMBS * 8 + 15) / 16);
     const size_t work = F::LIMBS == 4 ? (n + 1) / 2 : ((F::LIMBS == 1 ? (n + 1) / 2 : n) + 3) / 4;
-    if (F::LIMBS == 1 && !aligned16(dst))  // an 8-byte aligned window of a larger vector: element-wise stores
-      AES4_LAUNCH((k_vector_random<F, false>), work, S(stream), ctx, dst, key, (u64)counter0, n);
-    else
-      AES4_LAUNCH((k_vector_random<F, true>), work, S(stream), ctx, dst, key, (u64)counter0, n);
-    LAUNCH_CHECK();
+    // an 8-byte aligned window of a larger vector: element-wise stores
+    auto kern = F::LIMBS == 1 && !aligned16(dst) ? &k_vector_random<F, false> : &k_vector_random<F, true>;
+    HIP_TRY(launch_aes4(kern, work, S(stream), ctx, dst, key, (u64)counter0, n));
     return SCL_OK;
   });
 }
@@ -1733,17 +1374,14 @@ static int launch_gfpos(bool big_block, u64* out, const u64* shares, size_t stri
                         hipStream_t st) {
   const size_t lds = gfpos_lds_bytes(m);
   if (!big_block) {  // two 512-thread workgroups per CU
-    auto kern = &k_recover_gf128_pos<512, 2>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const size_t blocks = (N + 511) / 512;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(512), lds, st, out, shares, stride, big, (int)m, N);
+    HIP_TRY(launch_lds(&k_recover_gf128_pos<512, 2>, dim3((unsigned)(blocks < 512 ? blocks : 512)), dim3(512), lds, st, out, shares,
+                       stride, big, (int)m, N));
   } else {           // one 1024-thread workgroup per CU
-    auto kern = &k_recover_gf128_pos<1024, 1>;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const size_t blocks = (N + 1023) / 1024;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(1024), lds, st, out, shares, stride, big, (int)m, N);
+    HIP_TRY(launch_lds(&k_recover_gf128_pos<1024, 1>, dim3((unsigned)(blocks < 256 ? blocks : 256)), dim3(1024), lds, st, out, shares,
+                       stride, big, (int)m, N));
   }
-  LAUNCH_CHECK();
   return SCL_OK;
 }
 
@@ -1768,7 +1406,7 @@ static int recover_block(int field, uint64_t* out, const uint64_t* shares, size_
       // Montgomery fields: coefficients that are small signed integers (the default nodes' binomials) need no Montgomery product
       SmallLam sl;
       if (!prev && small_lambda<F>(ctx, lambda_host, m, sl))
-        return RecoverSmall<F, FIXED_M_MAX>::run(ctx, out, shares, stride, sl, (int)m, N, S(stream));
+        return recover_small<F>(ctx, out, shares, stride, sl, (int)m, N, S(stream));
     }
     if constexpr (F::TAG == 3) {
       const long ft = g_force_table.load();
@@ -1796,7 +1434,7 @@ static int recover_block(int field, uint64_t* out, const uint64_t* shares, size_
       const u64* sh = shares + first * F::LIMBS;
       if (fixed) {
         if constexpr (F::TAG <= 1) {
-          SCL_TRY((RecoverFixed<F, FIXED_M_MAX>::template run<VEC>(ctx, o, sh, stride, lam, (int)m, npacks, S(stream))));
+          SCL_TRY((recover_fixed<F, VEC>(ctx, o, sh, stride, lam, (int)m, npacks, S(stream))));
         }
       } else {
         hipLaunchKernelGGL((k_recover_table<F, VEC>), dim3(grid_for(npacks)), dim3(BLOCK), 0, S(stream), ctx, o, sh, stride,
@@ -1807,7 +1445,6 @@ static int recover_block(int field, uint64_t* out, const uint64_t* shares, size_
     });
   });
 }
-
 
 int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const uint64_t* secrets,
                          const uint64_t* coeffs, size_t coeff_stride, size_t N, size_t t, size_t n,
@@ -1882,17 +1519,11 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
             if (sw > 0 && (F::LIMBS == 1 || sw128 > 0)) {
               const size_t pad = residency_pad(F::LIMBS == 1 ? sw : sw128, 64, sizeof(u32) * SmallVdm::CAP);
               const dim3 g(grid_for_block(npacks, 64));
-#define SST_CASE(TT)                                                                                                     \
-  case TT:                                                                                                               \
-    hipLaunchKernelGGL((k_share_small_t<F, VEC, TT>), g, dim3(64), pad, S(stream), ctx, shares + first * F::LIMBS, share_stride, \
-                       secrets + first * F::LIMBS, coeffs + first * F::LIMBS, coeff_stride, sv, (int)n, npacks);         \
-    launched = true;                                                                                                     \
-    break;
-              switch (t) {
-                SST_CASE(1) SST_CASE(2) SST_CASE(3) SST_CASE(4) SST_CASE(5) SST_CASE(6) SST_CASE(7)
-                default: break;
-              }
-#undef SST_CASE
+              launched = dispatch_int<1, 7>((long)t, [&](auto TT) {
+                hipLaunchKernelGGL((k_share_small_t<F, VEC, decltype(TT)::value>), g, dim3(64), pad, S(stream), ctx,
+                                   shares + first * F::LIMBS, share_stride, secrets + first * F::LIMBS, coeffs + first * F::LIMBS,
+                                   coeff_stride, sv, (int)n, npacks);
+              });
             }
           }
           if constexpr (F::LIMBS == 4) {
@@ -1903,17 +1534,11 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
               // (the default cap of the 16-byte fields is 12; the lane pairs run best at 14-16: profiles/r5_probe_f3_waves.txt)
               const size_t pad = residency_pad(sw128 == 12 ? 16 : sw128, 64, sizeof(u32) * SmallVdm::CAP);
               const dim3 g(grid_for_block(2 * npacks, 64));
-#define SSP_CASE(TT)                                                                                                     \
-  case TT:                                                                                                               \
-    hipLaunchKernelGGL((k_share_small_pair<F, TT>), g, dim3(64), pad, S(stream), ctx, shares + first * F::LIMBS, share_stride, \
-                       secrets + first * F::LIMBS, coeffs + first * F::LIMBS, coeff_stride, sv, (int)n, npacks);         \
-    launched = true;                                                                                                     \
-    break;
-              switch (t) {
-                SSP_CASE(1) SSP_CASE(2) SSP_CASE(3) SSP_CASE(4) SSP_CASE(5) SSP_CASE(6) SSP_CASE(7)
-                default: break;
-              }
-#undef SSP_CASE
+              launched = dispatch_int<1, 7>((long)t, [&](auto TT) {
+                hipLaunchKernelGGL((k_share_small_pair<F, decltype(TT)::value>), g, dim3(64), pad, S(stream), ctx,
+                                   shares + first * F::LIMBS, share_stride, secrets + first * F::LIMBS, coeffs + first * F::LIMBS,
+                                   coeff_stride, sv, (int)n, npacks);
+              });
             }
           }
           if (!launched)
@@ -1935,12 +1560,10 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
           const u64* se = secrets + first * F::LIMBS;
           const u64* co = coeffs + first * F::LIMBS;
           const dim3 g(grid_for(npacks)), blk(BLOCK);
-#define BLK_LAUNCH(GG) \
-  hipLaunchKernelGGL((k_share_blocked<F, VEC, GG>), g, blk, 0, S(stream), ctx, sh, share_stride, se, co, coeff_stride, bv, (int)t, (int)n, npacks)
-          if (G == 8) BLK_LAUNCH(8);
-          else if (G == 6) BLK_LAUNCH(6);
-          else BLK_LAUNCH(4);
-#undef BLK_LAUNCH
+          dispatch_of<8, 6, 4>(G, [&](auto GG) {  // (blocked_vandermonde: one of the three, or 0)
+            hipLaunchKernelGGL((k_share_blocked<F, VEC, decltype(GG)::value>), g, blk, 0, S(stream), ctx, sh, share_stride, se, co,
+                               coeff_stride, bv, (int)t, (int)n, npacks);
+          });
           LAUNCH_CHECK();
           return SCL_OK;
         });
@@ -1968,15 +1591,6 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
       const u64* se = secrets + first * F::LIMBS;
       const u64* co = coeffs ? coeffs + first * F::LIMBS : nullptr;
       const dim3 g(grid_for(npacks)), blk(BLOCK);
-#define SHARE_LAUNCH(TREG)                                                                                        \
-  do {                                                                                                            \
-    if (smallx)                                                                                                   \
-      hipLaunchKernelGGL((k_share<F, VEC, TREG, true>), g, blk, 0, S(stream), ctx, sh, share_stride, se, co,      \
-                         coeff_stride, alx, (int)t, (int)n, npacks);                                              \
-    else                                                                                                          \
-      hipLaunchKernelGGL((k_share<F, VEC, TREG, false>), g, blk, 0, S(stream), ctx, sh, share_stride, se, co,     \
-                         coeff_stride, al, (int)t, (int)n, npacks);                                               \
-  } while (0)
       bool launched = false;
       if constexpr (F::TAG == 3) {
         if (smallx && t >= 5 && t <= 16 && !g_force_table.load()) {  // per-node Horner code ("force_table" 1: the tested-bits form)
@@ -1986,16 +1600,10 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
           bool default_nodes_in_order = n <= 64 && g_gf_tiles.load() != 0;
           for (size_t i = 0; i < n && default_nodes_in_order; ++i) default_nodes_in_order = (u128)al.v[i] == (u128)(i + 1);
           if (default_nodes_in_order) {  // party i at the bit pattern of i + 1: eight nodes per Horner loop
-#define GFT_CASE(TT)                                                                                                          \
-  case TT:                                                                                                                    \
-    hipLaunchKernelGGL(k_share_gf_tiles<TT>, gg, blk, 0, S(stream), sh, share_stride, se, co, coeff_stride, (int)n, npacks); \
-    break;
-            switch (t) {
-              GFT_CASE(5) GFT_CASE(6) GFT_CASE(7) GFT_CASE(8) GFT_CASE(9) GFT_CASE(10) GFT_CASE(11) GFT_CASE(12) GFT_CASE(13)
-              GFT_CASE(14) GFT_CASE(15) GFT_CASE(16)
-              default: break;
-            }
-#undef GFT_CASE
+            dispatch_int<5, 16>((long)t, [&](auto TT) {  // (5 <= t <= 16 here)
+              hipLaunchKernelGGL(k_share_gf_tiles<decltype(TT)::value>, gg, blk, 0, S(stream), sh, share_stride, se, co, coeff_stride,
+                                 (int)n, npacks);
+            });
           } else {
             hipLaunchKernelGGL(k_share_gf_nodes<F>, gg, blk, 0, S(stream), sh, share_stride, se, co, coeff_stride, al, (int)t, (int)n,
                                npacks);
@@ -2003,11 +1611,16 @@ int scl_hip_shamir_share(int field, uint64_t* shares, size_t share_stride, const
           launched = true;
         }
       }
-      if (launched) {
-      } else if (t <= 4) SHARE_LAUNCH(4);
-      else if (t <= 16) SHARE_LAUNCH(16);
-      else SHARE_LAUNCH(48);
-#undef SHARE_LAUNCH
+      if (!launched)  // coefficients in registers: 4, 16 or 48 of them
+        dispatch_of<4, 16, 48>(t <= 4 ? 4 : t <= 16 ? 16 : 48, [&](auto TR) {
+          constexpr int TREG = decltype(TR)::value;
+          if (smallx)
+            hipLaunchKernelGGL((k_share<F, VEC, TREG, true>), g, blk, 0, S(stream), ctx, sh, share_stride, se, co, coeff_stride, alx,
+                               (int)t, (int)n, npacks);
+          else
+            hipLaunchKernelGGL((k_share<F, VEC, TREG, false>), g, blk, 0, S(stream), ctx, sh, share_stride, se, co, coeff_stride, al,
+                               (int)t, (int)n, npacks);
+        });
       LAUNCH_CHECK();
       return SCL_OK;
     });
@@ -2049,8 +1662,7 @@ static int share_prg_two_pass(int field, uint64_t* shares, size_t share_stride, 
     const size_t c = N - s0 < slab ? N - s0 : slab;
     rc = with_field(field, [&](auto f, auto ctx) -> int {
       using F = decltype(f);
-      AES4_LAUNCH((k_prg_coeff_rows<F>), c, S(stream), ctx, rows, rstride, key, (u64)(counter0 + s0 * B), (int)t, c, lane);
-      LAUNCH_CHECK();
+      HIP_TRY(launch_aes4(&k_prg_coeff_rows<F>, c, S(stream), ctx, rows, rstride, key, (u64)(counter0 + s0 * B), (int)t, c, lane));
       return SCL_OK;
     });
     if (rc == SCL_OK)
@@ -2137,32 +1749,20 @@ static int share_prg_impl(int field, uint64_t* shares, size_t share_stride, cons
           constexpr int VEC = decltype(V)::value;
           const int nblk = F::LIMBS == 1 ? (int)(t / 2 + 1) : (int)t;
           if (t == 3) {  // BASELINE's threshold: the term loop compiled in (profiles/r3_probe_prg_t3.txt)
-            AES4_LAUNCH((k_share_prg_small_t<F, VEC, (F::LIMBS == 1 ? 2 : 3), 3>), npacks, S(stream), shares + first * F::LIMBS,
-                        share_stride, secrets + first * F::LIMBS, key, (u64)(counter0 + first * blocks_per_secret), sv, (int)n,
-                        npacks);
-            LAUNCH_CHECK();
+            HIP_TRY(launch_aes4(&k_share_prg_small_t<F, VEC, (F::LIMBS == 1 ? 2 : 3), 3>, npacks, S(stream), shares + first * F::LIMBS,
+                                share_stride, secrets + first * F::LIMBS, key, (u64)(counter0 + first * blocks_per_secret), sv, (int)n,
+                                npacks));
             return SCL_OK;
           }
-#define SPS_CASE(NB)                                                                                          \
-  case NB:                                                                                                    \
-    AES4_LAUNCH((k_share_prg_small<F, VEC, NB>), npacks, S(stream), shares + first * F::LIMBS, share_stride,   \
-                secrets + first * F::LIMBS, key, (u64)(counter0 + first * blocks_per_secret), sv, (int)t, (int)n,  \
-                npacks);                                                                                      \
-    break;
-          switch (nblk) {
-            SPS_CASE(1) SPS_CASE(2) SPS_CASE(3) SPS_CASE(4)
-            default:
-              if constexpr (F::LIMBS == 2) {
-                switch (nblk) {
-                  SPS_CASE(5) SPS_CASE(6) SPS_CASE(7)
-                  default: return fail(SCL_ERR_BAD_ARG, "share_prg: internal block count");
-                }
-              } else {
-                return fail(SCL_ERR_BAD_ARG, "share_prg: internal block count");
-              }
-          }
-#undef SPS_CASE
-          LAUNCH_CHECK();
+          // AES blocks per secret compiled in: 1..4, and 5..7 for the 16-byte field
+          hipError_t launch_status = hipSuccess;
+          if (!dispatch_int<1, (F::LIMBS == 2 ? 7 : 4)>(nblk, [&](auto NB) {
+                launch_status = launch_aes4(&k_share_prg_small<F, VEC, decltype(NB)::value>, npacks, S(stream), shares + first * F::LIMBS,
+                                share_stride, secrets + first * F::LIMBS, key, (u64)(counter0 + first * blocks_per_secret), sv, (int)t,
+                                (int)n, npacks);
+              }))
+            return fail(SCL_ERR_BAD_ARG, "share_prg: internal block count");
+          HIP_TRY(launch_status);
           return SCL_OK;
         });
       }
@@ -2187,29 +1787,24 @@ static int share_prg_impl(int field, uint64_t* shares, size_t share_stride, cons
       constexpr int VEC = decltype(V)::value;
       u64* sh = shares + first * F::LIMBS;
       const u64* se = secrets + first * F::LIMBS;
-#define SHAREP_LAUNCH1(TREG, SX)                                                                                 \
-  do {                                                                                                           \
-    const BigTable<F>& nodes_ = SX ? alx : al;                                                                   \
-    if constexpr (share_prg_four_tables<F, TREG>())                                                              \
-      AES4_LAUNCH((k_share_prg<F, VEC, TREG, SX>), npacks, S(stream), ctx, sh, share_stride, se, key,            \
-                  (u64)(counter0 + first * blocks_per_secret), nodes_, (int)t, (int)n, npacks, lane);            \
-    else                                                                                                         \
-      hipLaunchKernelGGL((k_share_prg<F, VEC, TREG, SX>), dim3(grid_aes(npacks)), dim3(BLOCK), 0, S(stream), ctx, \
-                         sh, share_stride, se, key, (u64)(counter0 + first * blocks_per_secret), nodes_, (int)t, \
-                         (int)n, npacks, lane);                                                                  \
-  } while (0)
-#define SHAREP_LAUNCH(TREG)                                                                                      \
-  do {                                                                                                           \
-    if (smallx) SHAREP_LAUNCH1(TREG, true);                                                                      \
-    else SHAREP_LAUNCH1(TREG, false);                                                                            \
-  } while (0)
-      if (t <= 4) SHAREP_LAUNCH(4);
-      else if (t <= 16) SHAREP_LAUNCH(16);
-      else SHAREP_LAUNCH(48);
-#undef SHAREP_LAUNCH
-#undef SHAREP_LAUNCH1
-      LAUNCH_CHECK();
-      return SCL_OK;
+      // coefficients in registers: 4, 16 or 48 of them; nodes as small constants where they are (SX)
+      auto launch = [&](auto TR, auto SXc) -> int {
+        constexpr int TREG = decltype(TR)::value;
+        constexpr bool SX = decltype(SXc)::value;
+        auto kern = &k_share_prg<F, VEC, TREG, SX>;
+        const BigTable<F>& nodes = SX ? alx : al;
+        // the four-table AES kernels with their 128 KiB of LDS where the kernel is one, the replicated table's grid elsewhere
+        constexpr bool four = share_prg_four_tables<F, TREG>();
+        HIP_TRY(launch_lds(kern, dim3(four ? grid_aes4(npacks) : grid_aes(npacks)), dim3(four ? ABLOCK : BLOCK),
+                           four ? (size_t)AES4_LDS_BYTES : 0, S(stream), ctx, sh, share_stride, se, key,
+                           (u64)(counter0 + first * blocks_per_secret), nodes, (int)t, (int)n, npacks, lane));
+        return SCL_OK;
+      };
+      int rc = SCL_OK;
+      dispatch_of<4, 16, 48>(t <= 4 ? 4 : t <= 16 ? 16 : 48, [&](auto TR) {
+        rc = smallx ? launch(TR, std::true_type{}) : launch(TR, std::false_type{});
+      });
+      return rc;
     });
   });
 }
@@ -2285,14 +1880,10 @@ int scl_hip_shamir_recover_detect(int field, uint64_t* out, unsigned char* statu
       auto launch = [&](auto RBc) -> int {
         constexpr int RB = decltype(RBc)::value;
         auto kern = &k_recover_detect<F, VEC, RB>;
-        if (lbytes > 48 * 1024)
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lbytes));
         const size_t blocks = (npacks + BLOCK - 1) / BLOCK;  // one pack per thread (the kernel has barriers)
         if (blocks > 0x7fffffffull) return fail(SCL_ERR_BAD_ARG, "recover_detect: batch too large for one launch");
-        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(BLOCK), lbytes, S(stream), ctx, out + first * F::LIMBS,
-                           status + first, shares + first * F::LIMBS, stride, L_dev, (int)d1, (int)nchk, npacks, cnt);
-        LAUNCH_CHECK();
+        HIP_TRY(launch_lds(kern, dim3((unsigned)blocks), dim3(BLOCK), lbytes, S(stream), ctx, out + first * F::LIMBS, status + first,
+                           shares + first * F::LIMBS, stride, L_dev, (int)d1, (int)nchk, npacks, cnt));
         return SCL_OK;
       };
       if constexpr (F::LIMBS >= 4) {
@@ -2399,30 +1990,20 @@ int scl_hip_shamir_recover_correct(int field, uint64_t* f_out, size_t f_stride, 
       HIP_TRY(hipMemsetAsync(counters, 0, 8, S(stream)));
       HIP_TRY(hipMemcpyAsync(L_dev, Lk.data(), Lk.size() * sizeof(KC), hipMemcpyHostToDevice, S(stream)));
       HIP_TRY(hipMemcpyAsync(nodes_dev, alphas.data(), nbytes, hipMemcpyHostToDevice, S(stream)));
-      auto kern = &k_bw_consistent<F, RB>;
-      if (lbytes > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lbytes));
       // one secret per thread (the kernel has barriers); N < 2^32 was checked above
-      hipLaunchKernelGGL(kern, dim3((unsigned)((N + BLOCK - 1) / BLOCK)), dim3(BLOCK), lbytes, S(stream), ctx, f_out,
+      HIP_TRY(launch_lds(&k_bw_consistent<F, RB>, dim3((unsigned)((N + BLOCK - 1) / BLOCK)), dim3(BLOCK), lbytes, S(stream), ctx, f_out,
                          f_stride, e_out, e_stride, status, nerr, shares, stride, L_dev, (int)d1, (int)nchk, N,
-                         static_cast<unsigned*>(queue), counters);
-      LAUNCH_CHECK();
+                         static_cast<unsigned*>(queue), counters));
       unsigned h[2] = {0, 0};
       HIP_TRY(hipMemcpyAsync(h, counters, 8, hipMemcpyDeviceToHost, S(stream)));
       HIP_TRY(hipStreamSynchronize(S(stream)));
       if (num_queued_host) *num_queued_host = h[0];
       if (h[0] == 0) return SCL_OK;
       const size_t lds = in_lds ? solve_bytes : 0;
-      if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bw_solve<F>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       const unsigned grid = (unsigned)std::min<size_t>(h[0], groups_cap);
       const unsigned threads = (unsigned)std::min<size_t>(1024, (n + BW_WAVE - 1) / BW_WAVE * BW_WAVE);  // threads over rows
-      hipLaunchKernelGGL((k_bw_solve<F>), dim3(grid), dim3(threads), lds, S(stream), ctx, f_out, f_stride, e_out, e_stride,
-                         status, nerr, shares, stride, nodes_dev, (int)n, static_cast<const unsigned*>(queue), h[0],
-                         counters + 1, work);
-      LAUNCH_CHECK();
+      HIP_TRY(launch_lds(&k_bw_solve<F>, dim3(grid), dim3(threads), lds, S(stream), ctx, f_out, f_stride, e_out, e_stride, status,
+                         nerr, shares, stride, nodes_dev, (int)n, static_cast<const unsigned*>(queue), h[0], counters + 1, work));
       HIP_TRY(hipMemcpyAsync(h, counters, 8, hipMemcpyDeviceToHost, S(stream)));
       HIP_TRY(hipStreamSynchronize(S(stream)));
       if (num_failed_host) *num_failed_host = h[1];
@@ -2478,10 +2059,9 @@ int scl_hip_additive_share_prg(int field, uint64_t* shares, size_t share_stride,
     const int vec = vec_width<F>({shares, secrets}, {share_stride});
     return split_vec<F>(vec, N, [&](auto V, size_t first, size_t npacks) -> int {
       constexpr int VEC = decltype(V)::value;
-      AES4_LAUNCH((k_additive_share_prg<F, VEC>), npacks, S(stream), ctx, shares + first * F::LIMBS, share_stride,
-                  secrets + first * F::LIMBS, key, (u64)(counter0 + first * (n - 1) * ((F::LIMBS * 8 + 15) / 16)), (int)n,
-                  npacks);
-      LAUNCH_CHECK();
+      HIP_TRY(launch_aes4(&k_additive_share_prg<F, VEC>, npacks, S(stream), ctx, shares + first * F::LIMBS, share_stride,
+                          secrets + first * F::LIMBS, key, (u64)(counter0 + first * (n - 1) * ((F::LIMBS * 8 + 15) / 16)), (int)n,
+                          npacks));
       return SCL_OK;
     });
   });
@@ -2672,19 +2252,10 @@ static int transpose_impl(int field, uint64_t* dst, const uint64_t* src, size_t 
       const size_t ntiles16 = (N + t16 - 1) / t16;
       const unsigned g16 = (unsigned)(ntiles16 < (1u << 20) ? ntiles16 : (1u << 20));
       const size_t shmem16 = t16 * n * (size_t)L * 8;
-#define TR16_LAUNCH(LL, SOA) \
-  hipLaunchKernelGGL((k_transpose16<LL, SOA>), dim3(g16), dim3(BLOCK), shmem16, S(stream), dst, src, stride, N, (int)n, (int)t16)
-      if (L == 1) {
-        if (to_soa) TR16_LAUNCH(1, true);
-        else TR16_LAUNCH(1, false);
-      } else if (L == 2) {
-        if (to_soa) TR16_LAUNCH(2, true);
-        else TR16_LAUNCH(2, false);
-      } else {
-        if (to_soa) TR16_LAUNCH(4, true);
-        else TR16_LAUNCH(4, false);
-      }
-#undef TR16_LAUNCH
+      dispatch_of<1, 2, 4>(L, [&](auto LL) {  // (scl_hip_limbs: one of the three)
+        auto kern = to_soa ? &k_transpose16<decltype(LL)::value, true> : &k_transpose16<decltype(LL)::value, false>;
+        hipLaunchKernelGGL(kern, dim3(g16), dim3(BLOCK), shmem16, S(stream), dst, src, stride, N, (int)n, (int)t16);
+      });
       LAUNCH_CHECK();
       return SCL_OK;
     }
@@ -2696,19 +2267,10 @@ static int transpose_impl(int field, uint64_t* dst, const uint64_t* src, size_t 
   const size_t ntiles = (N + tile - 1) / tile;
   const unsigned g = (unsigned)(ntiles < 8192 ? ntiles : 8192);
   const size_t shmem = tile * n * (size_t)L * 8;
-#define TR_LAUNCH(LL, SOA) \
-  hipLaunchKernelGGL((k_transpose<LL, SOA>), dim3(g), dim3(BLOCK), shmem, S(stream), dst, src, stride, N, (int)n, (int)tile)
-  if (L == 1) {
-    if (to_soa) TR_LAUNCH(1, true);
-    else TR_LAUNCH(1, false);
-  } else if (L == 2) {
-    if (to_soa) TR_LAUNCH(2, true);
-    else TR_LAUNCH(2, false);
-  } else {
-    if (to_soa) TR_LAUNCH(4, true);
-    else TR_LAUNCH(4, false);
-  }
-#undef TR_LAUNCH
+  dispatch_of<1, 2, 4>(L, [&](auto LL) {
+    auto kern = to_soa ? &k_transpose<decltype(LL)::value, true> : &k_transpose<decltype(LL)::value, false>;
+    hipLaunchKernelGGL(kern, dim3(g), dim3(BLOCK), shmem, S(stream), dst, src, stride, N, (int)n, (int)tile);
+  });
   LAUNCH_CHECK();
   return SCL_OK;
 }

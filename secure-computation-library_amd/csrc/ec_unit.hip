@@ -17,16 +17,7 @@ namespace sclhip {
 namespace {
 using namespace secp;
 
-// 64 lanes a block: one wave, and the whole register file of a SIMD lane is open to the compiler (no spilling at the price of
-// occupancy, which a kernel that waits for nothing but its own multiplier does not need much of)
-constexpr int EBLOCK = 64;
-#define SCL_EC_STRIDE(q, n) \
-  for (size_t q = (size_t)blockIdx.x * EBLOCK + threadIdx.x; q < (n); q += (size_t)gridDim.x * EBLOCK)
-
-inline unsigned ec_grid(size_t items) {
-  const size_t blocks = (items + EBLOCK - 1) / EBLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 0x7fffffffu ? 0x7fffffffu : blocks);
-}
+#include "ec_common.hpp"  // EBLOCK, SCL_EC_STRIDE, ec_grid
 
 // Vector<EC> element-wise: a + b, a - b, -a, 2a
 __global__ __launch_bounds__(EBLOCK) void k_ec_ew(int op, u64* dst, const u64* a, const u64* b, size_t n) {

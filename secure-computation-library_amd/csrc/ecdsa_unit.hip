@@ -19,25 +19,13 @@ namespace sclhip {
 namespace {
 using namespace secp;
 
-constexpr int EBLOCK = 64;
-constexpr size_t MUL_SLOTS_MAX = (size_t)1 << 17;  // 2 048 blocks: eight waves on each of 256 CUs
-#define SCL_EC_STRIDE(q, n) \
-  for (size_t q = (size_t)blockIdx.x * EBLOCK + threadIdx.x; q < (n); q += (size_t)gridDim.x * EBLOCK)
+#include "ec_common.hpp"  // EBLOCK, SCL_EC_STRIDE, ec_grid, raise_flag
 
-inline unsigned ec_grid(size_t items) {
-  const size_t blocks = (items + EBLOCK - 1) / EBLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 0x7fffffffu ? 0x7fffffffu : blocks);
-}
+constexpr size_t MUL_SLOTS_MAX = (size_t)1 << 17;  // 2 048 blocks: eight waves on each of 256 CUs
 // slots of the window-table scratch a call over n items uses: a whole number of blocks
 inline size_t mul_slots(size_t n) {
   const size_t s = (n + EBLOCK - 1) / EBLOCK * EBLOCK;
   return s < MUL_SLOTS_MAX ? s : MUL_SLOTS_MAX;
-}
-
-// as raise_flag of kernels.hpp: the only bit anyone sets in the word is this one, so a plain store of 1 is the OR
-__device__ __forceinline__ void raise_flag(unsigned* flag) {
-  if (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0)
-    __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // dst[i] = scalars[i] * points[i].  The lane's table: scratch + slot * 12, entries gridDim.x * 64 * 12 limbs apart.

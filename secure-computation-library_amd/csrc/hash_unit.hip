@@ -179,61 +179,11 @@ hipError_t hash_launch_verify(unsigned char* ok, const unsigned char* leaf_diges
 }  // namespace sclhip
 
 // ---- the entry points ------------------------------------------------------------------------------------------------------
-// State this unit shares with the units of capi.hip (defined in the common one, see there): the thread's last diagnostic
-// (unit_host.hpp) and its temporary arenas.  TempArena is capi.hip's struct, member for member.
-struct TempArena {
-  int device = -1;
-  void* dev = nullptr;
-  size_t bytes = 0;
-  hipEvent_t done = nullptr;
-  bool pending = false;
-};
-namespace sclhip_state {
-extern thread_local TempArena g_temps[2];
-}  // namespace sclhip_state
-
-#define SCL_UNIT_ENGINE
-#include "unit_host.hpp"
+// The thread's last diagnostic and its temporary arenas (temp_acquire / temp_release on arena 0) are the engine's.
+#include "engine_state.hpp"
 
 namespace {
 using namespace sclhip;
-
-// the discipline of capi.hip's temp_acquire / temp_release on arena 0: one buffer per host thread, kept and grown; an event
-// recorded after the last use makes the next user -- possibly on another stream -- wait for it; beyond 1 GiB it is given back
-int arena_acquire(size_t bytes, hipStream_t st, void** out) {
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  TempArena& a = sclhip_state::g_temps[0];
-  if (a.dev && (a.device != dev || a.bytes < bytes)) {
-    if (a.pending) HIP_TRY(hipEventSynchronize(a.done));
-    (void)hipFree(a.dev);
-    (void)hipEventDestroy(a.done);
-    a = TempArena{};
-  }
-  if (!a.dev) {
-    const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    HIP_TRY(hipMalloc(&a.dev, want));
-    HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-    a.device = dev;
-    a.bytes = want;
-  }
-  if (a.pending) HIP_TRY(hipStreamWaitEvent(st, a.done, 0));
-  *out = a.dev;
-  return SCL_OK;
-}
-int arena_release(hipStream_t st) {
-  TempArena& a = sclhip_state::g_temps[0];
-  if (a.dev && a.bytes > ((size_t)1 << 30)) {
-    HIP_TRY(hipStreamSynchronize(st));
-    (void)hipFree(a.dev);
-    (void)hipEventDestroy(a.done);
-    a = TempArena{};
-    return SCL_OK;
-  }
-  HIP_TRY(hipEventRecord(a.done, st));
-  a.pending = true;
-  return SCL_OK;
-}
 
 int merkle_shape_check(const char* what, size_t L, size_t T) {
   if (L == 0) return fail(SCL_ERR_BAD_ARG, std::string(what) + ": a tree has at least one leaf");
@@ -293,7 +243,7 @@ int scl_hip_merkle_root(unsigned char* roots, const unsigned char* leaf_digests,
     return SCL_OK;
   }
   void* tmp = nullptr;
-  SCL_TRY(arena_acquire((n1 + n2) * T * 32, S(stream), &tmp));
+  SCL_TRY(temp_acquire((n1 + n2) * T * 32, S(stream), &tmp));
   unsigned char* buf[2] = {static_cast<unsigned char*>(tmp), static_cast<unsigned char*>(tmp) + n1 * T * 32};
   const unsigned char* in = leaf_digests;
   int which = 0;
@@ -305,7 +255,7 @@ int scl_hip_merkle_root(unsigned char* roots, const unsigned char* leaf_digests,
     in = out;
     which ^= 1;
   }
-  return arena_release(S(stream));
+  return temp_release(S(stream));
 }
 
 int scl_hip_merkle_paths(unsigned char* path, const unsigned char* tree, size_t L, size_t T, const uint64_t* leaf_index,

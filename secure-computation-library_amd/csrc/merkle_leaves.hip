@@ -8,8 +8,6 @@
 // fields' own (detail/field.hpp: from_mont, to_be_image); an element is at most 32 bytes, one compression (sha256.hpp).
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-
 #include "tu_config.hpp"
 #if SCL_TU_FIELDS != 0xff
 #include "capi_names.inc"  // this unit's name for scl_hip_merkle_leaves
@@ -59,16 +57,8 @@ __global__ __launch_bounds__(BLOCK) void k_merkle_leaves(typename F::Ctx ctx, un
 }
 }  // namespace sclhip
 
-namespace sclhip_state {  // (defined by the common unit of capi.hip)
-extern thread_local Mont128::Ctx g_mont;
-extern std::mutex g_mont_default_mu;
-extern unsigned long g_mont_default_gen;
-extern thread_local unsigned long g_mont_gen;
-extern thread_local bool g_mont_own;
-}  // namespace sclhip_state
-
-#define SCL_UNIT_ENGINE
-#include "unit_host.hpp"
+// the field dispatch, the Mont128 latch rule and fail / alias_check: the engine's
+#include "engine_state.hpp"
 
 namespace {
 template <class F>
@@ -96,41 +86,7 @@ extern "C" int scl_hip_merkle_leaves(int field, unsigned char* digests, const ui
                                                     sclhip::alias::mat("a_dev", a, rows, stride, cols, (size_t)L * 8, false)});
         s != SCL_OK)
       return s;
-  [[maybe_unused]] const auto other_unit = [] { return fail(SCL_ERR_BAD_ARG, "field family not built into this translation unit"); };
-  switch (field) {
-    case SCL_M61:
-      if constexpr (SCL_TU_HAS(0)) return launch<M61>(M61::Ctx{}, digests, a, stride, cols, n, stream);
-      else return other_unit();
-    case SCL_M127:
-      if constexpr (SCL_TU_HAS(1)) return launch<M127>(M127::Ctx{}, digests, a, stride, cols, n, stream);
-      else return other_unit();
-    case SCL_MONT128:
-      if constexpr (SCL_TU_HAS(2)) {
-        // the calling thread's modulus, through the boundary that owns it (latched at first use; scl_hip.h) -- and, like every
-        // Mont128 call, not silently once the default it latched has been replaced (capi.hip, mont_check)
-        {
-          using namespace sclhip_state;
-          std::lock_guard<std::mutex> lk(g_mont_default_mu);
-          if (g_mont.p && !g_mont_own && g_mont_gen != g_mont_default_gen)
-            return fail(SCL_ERR_BAD_ARG, "mont128: the process-wide default modulus this thread latched has been changed; call "
-                                         "scl_hip_mont128_set_prime or scl_hip_mont128_relatch on this thread");
-        }
-        uint64_t p[2];
-        if (const int s = scl_hip_mont128_get_prime(p); s != SCL_OK) return s;
-        return launch<Mont128>(Mont128::make_ctx(((u128)p[1] << 64) | p[0]), digests, a, stride, cols, n, stream);
-      } else {
-        return other_unit();
-      }
-    case SCL_GF2_128:
-      if constexpr (SCL_TU_HAS(3)) return launch<Gf128>(Gf128::Ctx{}, digests, a, stride, cols, n, stream);
-      else return other_unit();
-    case SCL_SECP256K1_SCALAR:
-      if constexpr (SCL_TU_HAS(4)) return launch<Secp256k1Scalar>(Secp256k1Scalar::Ctx{}, digests, a, stride, cols, n, stream);
-      else return other_unit();
-    case SCL_SECP256K1_FIELD:
-      if constexpr (SCL_TU_HAS(5)) return launch<Secp256k1Field>(Secp256k1Field::Ctx{}, digests, a, stride, cols, n, stream);
-      else return other_unit();
-    default:  // the rings SCL_Z2K(K) too: the reference has no Serializer<Z2k>
-      return fail(SCL_ERR_BAD_ARG, "unknown field tag");
-  }
+  // (with_field refuses the rings SCL_Z2K(K) too: the reference has no Serializer<Z2k>; Mont128 computes over the calling thread's
+  // modulus, latched at first use, and not silently once the default it latched has been replaced: mont_check)
+  return with_field(field, [&](auto f, auto ctx) -> int { return launch<decltype(f)>(ctx, digests, a, stride, cols, n, stream); });
 }

@@ -13,15 +13,7 @@ namespace sclhip {
 namespace {
 using namespace secp;
 
-constexpr int EBLOCK = 64;
-#define SCL_EC_STRIDE(q, n) \
-  for (size_t q = (size_t)blockIdx.x * EBLOCK + threadIdx.x; q < (n); q += (size_t)gridDim.x * EBLOCK)
-
-inline unsigned ec_grid(size_t items) {
-  const size_t blocks = (items + EBLOCK - 1) / EBLOCK;
-  return (unsigned)(blocks < 1 ? 1 : blocks > 0x7fffffffu ? 0x7fffffffu : blocks);
-}
-constexpr size_t GRID_Y_MAX = 65535;
+#include "ec_common.hpp"  // EBLOCK, SCL_EC_STRIDE, ec_grid, GRID_Y_MAX
 
 // dst[row][i] = a[row][i] * G + b[row][i] * H from the two window tables: 128 mixed additions into one accumulator, no
 // doubling.  A zero digit is pt_add_mul_table's select, so no lane branches on its scalars.  Every operand has a row stride of

@@ -3,7 +3,7 @@
 // before the entry points.  Two macros, defined before the include, say what the unit is:
 //
 //   SCL_UNIT_ENGINE   a unit of libscl_hip.so (capi.hip, ec_, ecdsa_, pedersen_, hash_unit.hip, merkle_leaves.hip): the
-//                     diagnostics go to the engine's slot, sclhip_state::g_err, which capi.hip defines; the generic part only.
+//                     diagnostics go to the engine's slot, sclhip_state::g_err (engine_state.hpp; capi.hip's common unit defines it); the generic part only.
 //                     Without it the unit is an extension library beside the engine (libscl_hip_mpc / _prep / _hm / _ip / _vf / _rb / _fx):
 //                     it owns its slot and, serving every field from one unit, takes the field part too: the dispatch on the
 //                     field tag and the latch rule, the checks the entry points share (check_align, check_ptr,
@@ -28,7 +28,7 @@
 // ---- the generic part ------------------------------------------------------------------------------------------------------
 #ifdef SCL_UNIT_ENGINE
 namespace sclhip_state {
-extern thread_local std::string g_err;  // the thread's last diagnostic (defined in the common unit of capi.hip)
+extern thread_local std::string g_err;  // the thread's last diagnostic (engine_state.hpp; defined in the common unit of capi.hip)
 }  // namespace sclhip_state
 #endif
 

@@ -459,7 +459,12 @@ def test_shamir_golden(scl, f, name):
                                    (17, 16, 64), (1, 0, 5), (5, 4, 1),
                                    # 49..63 coefficients: one tile of the matrix-core kernel over Mersenne61 (since round 5; the
                                    # chunked Horner kernel for the other fields and for fewer than 1024 multiply-adds per secret)
-                                   (128, 63, 130), (70, 49, 90), (64, 50, 70), (60, 59, 33)])
+                                   (128, 63, 130), (70, 49, 90), (64, 50, 70), (60, 59, 33),
+                                   # every threshold the small-node kernels compile in (k_share_small_t / _pair: t = 1..7; the fused
+                                   # PRG kernels: 1..4 AES blocks per secret for Mersenne61, 1..7 for Mersenne127, t = 3 its own)
+                                   # and t = 8, the first past them; N = 129: a head of packs of two and the odd element
+                                   (10, 1, 129), (10, 2, 129), (10, 4, 129), (10, 5, 129), (10, 6, 129), (10, 7, 129), (10, 8, 129),
+                                   (18, 17, 65)])   # the first threshold past 16 on the Horner kernels (48 coefficients in registers)
 def test_shamir_share_recover_vs_oracle(scl, port, f, n, t, N):
     L = O.LIMBS[f]
     if f in SLOW_ORACLE:
@@ -691,7 +696,9 @@ def test_gf_tile_share_upper_tiles(scl, port, n):
 
 
 @pytest.mark.parametrize("n,t,N", [(128, 42, 300), (40, 13, 257), (10, 3, 1000), (33, 8, 31), (64, 31, 65), (65, 32, 96),
-                                   (5, 1, 7), (128, 48, 129), (1, 1, 40), (32, 31, 64)])
+                                   (5, 1, 7), (128, 48, 129), (1, 1, 40), (32, 31, 64),
+                                   # the five (k-steps, row tiles) pairs at their borders: (1,1) (1,2) (1,4) (2,2) (2,4)
+                                   (32, 31, 129), (33, 31, 129), (65, 31, 129), (32, 32, 129), (65, 32, 129)])
 def test_share_on_matrix_cores_vs_oracle(scl, port, n, t, N):
     """the i8-limb MFMA formulation of V * C (csrc/share_mfma.hpp) == per-secret Horner in the oracle"""
     f, L = O.M61, 1
@@ -721,7 +728,7 @@ def test_share_on_matrix_cores_vs_oracle(scl, port, n, t, N):
 @pytest.mark.parametrize("f", [O.M61, O.M127])
 def test_recover_fixed_table_and_scalar_kernels_agree(scl, port, f):
     L = O.LIMBS[f]
-    for m in (1, 2, 7, 8, 9, 15, 16, 17, 24, 33, 100, 128):
+    for m in (*range(1, 18), 24, 33, 100, 128):   # 1..16: k_recover_fixed<m>; beyond: the table kernel
         N = 515
         shares = rand_elems(port, f, m * N, b"tbl").reshape(m, N, L)
         lam = rand_elems(port, f, m, b"lam")
@@ -815,7 +822,9 @@ def test_recover_detect(scl, port, f, name):
     assert ei.value.reference_message == "not enough shares provided to detect errors"
 
 
-@pytest.mark.parametrize("t,d,extra,N", [(42, 42, 0, 5000), (23, 23, 1, 4100), (30, 20, 3, 4500), (63, 63, 0, 4200), (10, 60, 0, 4097)])
+@pytest.mark.parametrize("t,d,extra,N", [(42, 42, 0, 5000), (23, 23, 1, 4100), (30, 20, 3, 4500), (63, 63, 0, 4200), (10, 60, 0, 4097),
+                                         # rows = t, inner dimension d + 1: the five (k-steps, row tiles) pairs at their borders
+                                         (32, 31, 0, 129), (33, 31, 0, 129), (65, 31, 0, 129), (32, 32, 0, 129), (65, 32, 0, 129)])
 def test_recover_detect_on_matrix_cores(scl, port, t, d, extra, N):
     """shamirRecoverD over Mersenne61 with many check rows over many shares: the rows-times-shares product runs on the matrix
     cores (k_share_mfma_* as a matmul) and k_detect_compare does the checks.  Same statuses, values and count as the oracle
@@ -979,7 +988,9 @@ def test_matmul_vs_oracle(scl, port, f, M, K, N):
     assert np.array_equal(host(scl, scl.matmul(f, dev(scl, A), dev(scl, B))), port.matmul(f, A, B))
 
 
-@pytest.mark.parametrize("M,K,N", [(128, 43, 5000), (64, 22, 4099), (100, 64, 300), (1, 1, 70), (33, 5, 129), (16, 40, 4500), (32, 64, 700)])
+@pytest.mark.parametrize("M,K,N", [(128, 43, 5000), (64, 22, 4099), (100, 64, 300), (1, 1, 70), (33, 5, 129), (16, 40, 4500), (32, 64, 700),
+                                   # the five (k-steps, row tiles) pairs at their borders: (1,1) (1,2) (1,4) (2,2) (2,4)
+                                   (32, 32, 129), (33, 32, 129), (65, 32, 129), (32, 33, 129), (65, 33, 129)])
 def test_matmul_on_matrix_cores(scl, port, M, K, N):
     """Matrix::multiply with a small left factor through the i8-digit MFMA kernel == the oracle's i-k-j loop"""
     f, L = O.M61, 1
@@ -1026,7 +1037,8 @@ def test_matmul_has_no_bound_on_its_shape(scl, port, f, M, K, N):
 
 
 @pytest.mark.parametrize("M,K,N", [(300, 200, 5000), (129, 65, 4100), (128, 130, 4096), (1000, 64, 4500), (260, 7000, 4200),
-                                   (300, 300, 300), (65, 8300, 70), (33, 16500, 33), (97, 33, 131)])
+                                   (300, 300, 300), (65, 8300, 70), (33, 16500, 33), (97, 33, 131),
+                                   (129, 65, 129)])   # "mfma" 2: a second row block and a second k-chunk, each of one row / column
 def test_matmul_on_matrix_cores_beyond_one_tile(scl, port, M, K, N):
     """The matrix-core product beyond one 128 x 64 tile of the left factor == the oracle: the general kernel (gemm_mfma.hpp: digit
     planes of both factors in fragment order, K looped inside the kernel, super-steps of 8192 inner columns -- "mfma" 1), the
@@ -1064,7 +1076,7 @@ def test_matmul_on_matrix_cores_beyond_one_tile(scl, port, M, K, N):
 
 
 @pytest.mark.parametrize("f", ALL_FIELDS)
-@pytest.mark.parametrize("n,N", [(10, 5000), (10, 1027), (3, 513), (7, 64), (1, 100), (40, 1301), (128, 300), (10, 1)])
+@pytest.mark.parametrize("n,N", [(10, 5000), (10, 1027), (3, 513), (7, 64), (1, 100), (40, 1301), (128, 300), (10, 1), (3, 65)])
 def test_layout_bridge_both_ways(scl, port, f, n, N):
     """AoS [secret][party] (the reference's Vector per secret, shamir.h:52-68) <-> SoA [party][secret] through the 16-byte kernel
     (k_transpose16: ragged last tiles, odd secret counts, one party) and the 8-byte one ("force_scalar"), against numpy's
@@ -1097,7 +1109,7 @@ def test_layout_bridge_both_ways(scl, port, f, n, N):
 
 
 @pytest.mark.parametrize("f", [O.MONT128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD])
-@pytest.mark.parametrize("n", [1, 2, 3, 10, 16])
+@pytest.mark.parametrize("n", [1, 2, 3, 10, 16, 4, 5, 6, 7, 8, 9, 11, 12, 13, 14, 15])   # (k_recover_small<m>: every m = 1..16)
 def test_reconstruct_with_small_integer_coefficients(scl, port, f, n):
     """At the default nodes 1..n and x = 0 the Lagrange coefficients are the signed binomials (-1)^(i-1) C(n, i): over the
     Montgomery fields the reconstruct kernel then multiplies residues by plain small integers (k_recover_small) instead of

@@ -53,7 +53,7 @@ KNOBS, KNOB_DEFAULTS = _fuzz_abi_tables()
 # knob values a row uses beyond fuzz_abi's KNOBS, each with where it comes from (tests/test_redzone_model.py allows no others)
 EXTRA_KNOB_VALUES = {
     ("force_table", 3): "documented in include/scl_hip.h (GF(2^128) reconstruct on the shared-shift nibble tables) and taken at "
-                        "capi.hip:1841; fuzz_abi leaves it out because it only matters to one field's reconstruct",
+                        "recover_block's GF(2^128) branch; fuzz_abi leaves it out because it only matters to one field's reconstruct",
 }
 FIELDS6 = [O.M61, O.M127, O.MONT128, O.GF2_128, O.SECP256K1_SCALAR, O.SECP256K1_FIELD]     # fuzz_abi's FIELDS
 
@@ -409,13 +409,13 @@ def share_want(env, f, secrets, coeffs, n):
     return soa(env.port.shamir_share_coeffs(f, secrets, coeffs, n))
 
 
-# (n, t) across the dispatch of scl_hip_shamir_share (capi.hip:1878-2078): (10, 3) the small-node kernels; t = 4 | 5 and 16 | 17
-# either side of the register-specialised Horner range 5..16 (SHARE_LAUNCH 4 / 16 / 48, capi.hip:2070-2072; 32-byte elements take
-# the chunked kernel past 16, capi.hip:1904)
+# (n, t) across the dispatch of scl_hip_shamir_share (its with_field body in capi.hip): (10, 3) the small-node kernels; t = 4 | 5 and 16 | 17
+# either side of the register-specialised Horner range 5..16 (k_share with 4 / 16 / 48 coefficients in registers; 32-byte elements take
+# the chunked kernel past 16, share_chunked)
 SHARE_SHAPES = [(10, 3), (10, 4), (10, 5), (20, 16), (20, 17)]
 # Mersenne61 on the matrix cores ("mfma" 1).  One element past each kernel's column tile: k_share_mfma_m61_p16 and _pipe take 32
-# secrets per trip (capi.hip:739, 748: nblocks = (N + 31) / 32) -> 33; k_share_mfma_m61<KS, MT> takes 2 * (4 / MT) * 32 columns
-# (capi.hip:758) -> 129 for two row tiles (33..64 parties), 257 for one (already in BATCH)
+# secrets per trip (launch_share_mfma: nblocks = (N + 31) / 32) -> 33; k_share_mfma_m61<KS, MT> takes 2 * (4 / MT) * 32 columns
+# (launch_share_mfma) -> 129 for two row tiles (33..64 parties), 257 for one (already in BATCH)
 MFMA_SHARE = [((128, 42), [33]), ((100, 40), [33]), ((128, 63), [33]), ((100, 20), [33]), ((40, 13), [129]), ((10, 3), [])]
 
 
@@ -523,10 +523,10 @@ def run_shamir_recover(env, f, m):
         same(el(wd, f), want0[:N], note)
 
 
-# recover_detect (capi.hip:2275-2368), t = d, m = 2t + 1: nchk = t - 1 check rows and the value row, rows = t
-# (capi.hip:2295-2299).  Vector-ALU kernel: rows <= 4 take four rows per pass, more take eight (RBsel, capi.hip:2325; 32-byte elements two) -> t = 3, 5 and 9 (two row blocks).  Matrix
-# cores under "mfma" 1 (capi.hip:2305): rows * (d + 1) = 10 * 11 = 110 below 512, 23 * 24 = 552 above it (one row tile: 256 columns
-# per workgroup, 257 is in BATCH), and t = 40 with two k-steps and two row tiles: 128 columns (capi.hip:758) -> 129
+# recover_detect (scl_hip_shamir_recover_detect), t = d, m = 2t + 1: nchk = t - 1 check rows and the value row, rows = t
+# (its nchk and rows).  Vector-ALU kernel: rows <= 4 take four rows per pass, more take eight (RBsel; 32-byte elements two) -> t = 3, 5 and 9 (two row blocks).  Matrix
+# cores under "mfma" 1 (detect_mfma): rows * (d + 1) = 10 * 11 = 110 below 512, 23 * 24 = 552 above it (one row tile: 256 columns
+# per workgroup, 257 is in BATCH), and t = 40 with two k-steps and two row tiles: 128 columns (launch_share_mfma) -> 129
 DETECT = [(3, {}, ()), (5, {}, ()), (9, {}, ())]
 DETECT_MFMA = [(10, {"mfma": 1}, ()), (23, {"mfma": 1}, ()), (40, {"mfma": 1}, (129,))]
 
@@ -566,8 +566,8 @@ def run_shamir_recover_detect(env, f, t, extra):
             assert not got[bad_s].any(), note                 # out[s] = 0 where an error was detected (scl_hip.h)
 
 
-# Berlekamp-Welch (capi.hip:2371-2487): one shape in each storage regime of k_bw_solve.  n = 7: one wavefront; n = 67: the systems
-# in the workgroup's LDS for 8- and 16-byte elements (n <= 136 / 95, capi.hip:2434-2436) and ALREADY in the device-memory slice for
+# Berlekamp-Welch (scl_hip_shamir_recover_correct): one shape in each storage regime of k_bw_solve.  n = 7: one wavefront; n = 67: the systems
+# in the workgroup's LDS for 8- and 16-byte elements (n <= 136 / 95: in_lds) and ALREADY in the device-memory slice for
 # 32-byte elements (n <= 66); n = 148 over Mersenne61: the device-memory slice.  Secret s is clean, correctable (t errors) or
 # uncorrectable (t + 1 errors) by s mod 3, so the queued path writes f, err, nerr and status.
 @row("scl_hip_shamir_recover_correct",
@@ -690,27 +690,27 @@ def matmul_specs():
     out = []
     for f in FIELDS8:
         M, K, N = tiled_edge(f)
-        shapes = [(1, 1, 1), (3, 2, 1), (257, 3, 1),             # one column: k_matvec, a wavefront per row (capi.hip:2601)
+        shapes = [(1, 1, 1), (3, 2, 1), (257, 3, 1),             # one column: k_matvec, a wavefront per row (scl_hip_matmul, N == 1)
                   (2, 3, 3), (3, 5, 255), (M, K, N),
-                  (5, 513, 5)]                                   # K >= 512 and few tiles: slices of K to a temporary (capi.hip:2663)
+                  (5, 513, 5)]                                   # K >= 512 and few tiles: slices of K to a temporary (scl_hip_matmul, split)
         out.append((fname(f), dict(f=f, shapes=shapes), {"mfma": -1} if f == M61 else {}))
         if f == M61:    # what the shape picks by itself: the tiled kernel, the general matrix-core kernel, one matrix-core tile
             out.append(("m61-auto", dict(f=f, shapes=[(65, 17, 65), (33, 65, 33), (100, 43, 300)]), {}))
         # "matmul_lds_min" 1024: k_matmul_thin for K <= 16 (8 for 32-byte elements) and k_matmul beyond, a thread per (pack of)
-        # column(s) from 1024 columns (capi.hip:2632-2657); 1025 has the odd tail of split_vec
+        # column(s) from 1024 columns (scl_hip_matmul, k_matmul_thin); 1025 has the odd tail of split_vec
         out.append((fname(f) + "-matmul_lds_min=1024", dict(f=f, shapes=[(3, 5, 1025), (3, 17, 1025), (3, 5, 1024)]),
                     dict({"matmul_lds_min": 1024}, **({"mfma": -1} if f == M61 else {}))))
     for f in (M61, M127):
         out.append((fname(f) + "-matmul_lds_min=4096", dict(f=f, shapes=[(3, 5, 4097), (3, 17, 4097)]),
                     dict({"matmul_lds_min": 4096}, **({"mfma": -1} if f == M61 else {}))))
     # Mersenne61 on the matrix cores.  "mfma" 2: row blocks of 128 and k-chunks of 64 on the sharing kernels, the later chunks
-    # ADDING into C (capi.hip:805-821) -> 129 rows, 65 inner; columns one past the 32 / 128 / 256 of a trip (capi.hip:727, 758)
+    # ADDING into C (matmul_mfma_blocks) -> 129 rows, 65 inner; columns one past the 32 / 128 / 256 of a trip (launch_share_mfma)
     out.append(("m61-mfma=2", dict(f=M61, shapes=[(3, 2, 3), (33, 17, 257), (40, 33, 129), (129, 65, 33), (100, 130, 33)]), {"mfma": 2}))
-    # the general kernel (gemm_mfma.hpp): tiles of 32 x 32 x 32, a workgroup takes 2 x 2 tiles (capi.hip:828-830) -> 33 and 65 in
-    # every dimension; K = 1000 is 32 k-tiles, from where few workgroups split K into slices (capi.hip:834, needs ldc == N)
+    # the general kernel (gemm_mfma.hpp): tiles of 32 x 32 x 32, a workgroup takes 2 x 2 tiles (gemm_mfma_slab) -> 33 and 65 in
+    # every dimension; K = 1000 is 32 k-tiles, from where few workgroups split K into slices (gemm_mfma_slab, needs ldc == N)
     out.append(("m61-mfma=1-gemm", dict(f=M61, shapes=[(33, 65, 33), (65, 65, 65), (33, 97, 65), (34, 1000, 35)], dense=(34, 1000, 35)), {"mfma": 1}))
     # "gemm_slab_mib" 1: 65536 16-byte units per factor and launch; K = 1025 is 33 k-tiles of 512 units, so 3 tiles = 96 rows /
-    # columns per slab (capi.hip:854-858) -> 97 takes a second slab of one row and one column
+    # columns per slab (matmul_gemm_mfma) -> 97 takes a second slab of one row and one column
     for v in (1, 4):
         out.append((f"m61-mfma=1-gemm_slab_mib={v}", dict(f=M61, shapes=[(97, 1025, 97)]), {"mfma": 1, "gemm_slab_mib": v}))
     return out
@@ -738,9 +738,9 @@ def run_matmul(env, f, shapes, dense=None):
 
 # ---------------------------------------------------------------------------------------------- the layout bridge
 def transpose_edges(f, n, knobs):
-    """one secret past a tile of the layout kernels (transpose_impl, capi.hip:2689-2751): k_transpose16 takes the largest power
-    of two within min(40 KiB / (n L 8), "transpose_tile" or 512), at least 64 (capi.hip:2699-2707); k_transpose (odd strides,
-    8-byte alignment, "force_scalar") takes 32 KiB / (n L 8) capped at 1024, a multiple of 64 from 64 up (capi.hip:2729-2732)"""
+    """one secret past a tile of the layout kernels (transpose_impl in capi.hip): k_transpose16 takes the largest power
+    of two within min(40 KiB / (n L 8), "transpose_tile" or 512), at least 64 (t16); k_transpose (odd strides,
+    8-byte alignment, "force_scalar") takes 32 KiB / (n L 8) capped at 1024, a multiple of 64 from 64 up (tile)"""
     per = n * limbs(f) * 8
     t16 = min(40 * 1024 // per, knobs.get("transpose_tile", 0) or 512)
     t16 = max([p for p in (64, 128, 256, 512) if p <= t16], default=0)
