@@ -1,5 +1,5 @@
 """scl_amd._abi -- how the package binds a library of csrc/: the one loader and the one reader of a boundary header's prototypes,
-for the engine (scl_amd itself) and the extension libraries beside it (mpc, prep, hm, ip, vf, rb, fx).  Imports nothing of scl_amd."""
+for the engine (scl_amd itself) and the extension libraries beside it (mpc, prep, hm, ip, vf, rb, fx, cmp).  Imports nothing of scl_amd."""
 from __future__ import annotations
 
 import ctypes as C
